@@ -3,12 +3,25 @@
 Adam) on synthetic N=256 radar clouds at B=64 per GPU (BASELINE.json metric / configs[2]).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One process per GPU; batches shard over ranks (weak scaling: 64 pairs per GPU); the only
 collective is one RCCL all-reduce of the flat gradient bucket per step.  Rank 0 prints ONE
-JSON line.  The dominant hand-written kernel is cmf_gemm (the fp32 MFMA GEMM behind every 1x1 conv); every launch
+JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: `value` (frame-pairs/s of the timed region),
+`ms_per_step` (milliseconds per timed step), `metric`, `unit`, `higher_is_better`, `dtype`.  Every other figure of the line
+(the rooflines, the two extra timed regions, peak memory, BASELINE config 2, the all-reduce alone, the CPU baselines, the
+`--gemm-table`) is measured only with `--full`, which also brackets the large cmf_gemm launches of the timed region with HIP
+events; without it those fields are null.  `--dump-outputs DIR` writes what the last timed step returned (loss, loss items,
+model outputs, labels; for training also the flat gradient, the parameters and the float buffers after the step) as
+DIR/<name>.npy, float32 / float64, at most 64 MB in all; inputs and weights are seeded, so two builds run with the same
+arguments can be compared array for array.
+
+With `--full`: the dominant hand-written kernel is cmf_gemm (the fp32 MFMA GEMM behind every 1x1 conv); every launch
 >= 1 GFLOP is bracketed live with HIP events recorded INSIDE the library on the launch stream (the GEMMs of the
 set-conv block calls count too).  `roofline` = what the STEP extracts from the MFMA pipe: sum of 2*M*N*K over the
 bracketed launches of the timed region / the region's wall time (chains run on four streams, so per-launch
@@ -270,6 +283,57 @@ def clip_from_loader(batch, clip_len, rank, dev):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000          # (64 MB in decimal units: within 64 MiB as well)
+
+
+def step_outputs(a, result, net, step):
+    """Host copies of what one step of the timed path returned, by name: for training TrainStep's (loss, items, outputs, labels)
+    plus the flat gradient, the parameters and the float buffers the step left behind; for inference the model's outputs.
+    Call it right after the step, before anything else runs on the model."""
+    out = {}
+
+    def put(name, t):
+        if isinstance(t, torch.Tensor):
+            t = t.detach()
+            keep = t.dtype in (torch.float32, torch.float64)
+            out[name] = t.cpu().numpy() if keep else t.double().cpu().numpy()
+    if a.mode == "train":
+        loss, items, outs, labels = result
+        put("loss", loss)
+        for k in sorted(items):
+            put("loss_" + k, items[k])
+        heads = ("pred_flow", "output", "pre_trans", "mask") if a.model == "raflow" else ("pred_flow", "mseg_pre", "pre_trans", "mask")
+        for k, t in zip(heads, outs):
+            put(k, t)
+        for k, t in zip(("dyn_mask", "mseg_gt"), labels):
+            put(k, t)
+        put("grad", step.bucket.flat)
+        put("params", torch.cat([p.detach().reshape(-1) for p in net.parameters()]))
+        bufs = [b.detach().reshape(-1) for b in net.buffers() if b.is_floating_point()]
+        if bufs:
+            put("buffers", torch.cat(bufs))
+    else:
+        for i, t in enumerate(result):
+            put("out%d" % i, t)
+    return out
+
+
+def dump_outputs(arrays, d):
+    """Write `arrays` as d/<name>.npy within DUMP_BUDGET_BYTES: arrays are served smallest first, each to an equal share of what
+    is left; one over its share is replaced by a fixed, seeded sample of its flattened elements (indices in ascending order)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 256 * len(arrays)               # (.npy headers)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, v) in enumerate(items):
+        cap = max(1, left // (len(items) - i) // v.itemsize)
+        if v.size > cap:
+            idx = np.sort(np.random.default_rng(1234).choice(v.size, cap, replace=False))
+            v = np.ascontiguousarray(v.reshape(-1)[idx])
+        np.save(os.path.join(d, name + ".npy"), v)
+        left -= v.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -278,6 +342,12 @@ def main():
     ap.add_argument("--mode", choices=["train", "fwd"], default="train")
     ap.add_argument("--model", choices=["cmflow", "cmflow_t", "raflow"], default="cmflow")
     ap.add_argument("--batch", type=int, default=64, help="frame pairs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: rooflines (HIP events around the large cmf_gemm launches of the timed "
+                         "region), two more timed regions, peak memory, BASELINE config 2, the all-reduce alone, the op rooflines and the "
+                         "CPU baselines; without it the line carries value / ms_per_step and those fields are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--path", choices=["pm"], default="pm", help="pm: the fused point-major HIP path (the product has one path)")
     ap.add_argument("--serial", action="store_true",
@@ -297,6 +367,10 @@ def main():
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 100
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.gemm_table and not a.full:
+        ap.error("--gemm-table needs --full (the table comes from the bracketed launches)")
     host_cores = None
     if a.host_cores > 0:
         # in-process, before any HIP call (never a re-exec): the cores are taken from the allowed set in order, offset by the local
@@ -405,19 +479,21 @@ def main():
             f = frame[0] % len(clip)
             if a.model == "cmflow_t" and f == 0:
                 step.reset_clip()
-            step(clip[f])
+            r = step(clip[f])
             frame[0] += 1
+            return r
     else:
         net.eval()
+        step = None
 
         def one():
             with torch.no_grad():
                 if a.model == "cmflow_t":
-                    net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, "test", None)
+                    return net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, "test", None)
                 elif a.model == "raflow":
-                    net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], batch["interval"])
+                    return net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], batch["interval"])
                 else:
-                    net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, "test")
+                    return net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, "test")
 
     def fence():
         torch.cuda.synchronize()
@@ -431,20 +507,27 @@ def main():
     for _ in range(a.warmup):
         one()
     frame[0] = 0                                     # the timed region starts at the first frame of a clip
-    # HIP-event pairs around every 5th cmf_gemm launch >= 1 GFLOP, inside the library (all of them are counted; around every one the
-    # pairs themselves cost 0.13-0.18 ms per step: measured as the bracketed region against the unbracketed regions behind it)
-    _lib.SAMPLE_EVERY = 5                          # (coprime with the 44 such launches of a step: every launch position is sampled in turn)
-    _lib.profile_begin()
+    prof = None
+    if a.full:
+        # HIP-event pairs around every 5th cmf_gemm launch >= 1 GFLOP, inside the library (all of them are counted; around every one the
+        # pairs themselves cost 0.13-0.18 ms per step: measured as the bracketed region against the unbracketed regions behind it)
+        _lib.SAMPLE_EVERY = 5                          # (coprime with the 44 such launches of a step: every launch position is sampled in turn)
+        _lib.profile_begin()
     fence()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        one()
+    for _ in range(a.steps - 1):
+        one()                                        # (results dropped at once: outputs still reference the step's autograd graph)
+    last = one()
     fence()
     dt = time.perf_counter() - t0
-    prof = _lib.profile_end()
+    if a.full:
+        prof = _lib.profile_end()
+    # what the last timed step returned, copied before anything else runs on the model
+    dumped = step_outputs(a, last, net, step) if a.dump_outputs and rank == 0 else None
+    del last
     # run-to-run spread: two more timed regions of the same length, back to back (not part of `value`)
     spread = [dt / a.steps * 1e3]
-    for _ in range(2):
+    for _ in range(2 if a.full else 0):
         fence()
         t1 = time.perf_counter()
         for _ in range(a.steps):
@@ -506,7 +589,7 @@ def main():
     # the scales serialised (outside the timed region, not part of `value`) gives the kernel's own rate.
     # Every rank runs it: a training step contains the gradient all-reduce, a collective all ranks must enter.
     iso = iso_prof = None
-    if a.path == "pm":
+    if a.full and a.path == "pm":
         from cmflow_amd import fused_blocks as _FB
         _FB.set_serial(net, True)                   # the SAME launches, every chain on the caller's stream
         one(); torch.cuda.synchronize()
@@ -520,14 +603,16 @@ def main():
             iso["note"] = "3 extra steps with every chain on one stream (outside the timed region): the kernel's own rate"
 
     # peak device memory of the timed regions: torch's allocator (every tensor and arena of the step) + what the library holds itself
-    peak_mem = {"torch_max_allocated": int(torch.cuda.max_memory_allocated(dev)), "torch_max_reserved": int(torch.cuda.max_memory_reserved(dev)),
-                "library_scratch": int(_lib.lib().cmf_mem_stats())}
-    peak_mem["total"] = peak_mem["torch_max_allocated"] + peak_mem["library_scratch"]
+    peak_mem = None
+    if a.full:
+        peak_mem = {"torch_max_allocated": int(torch.cuda.max_memory_allocated(dev)), "torch_max_reserved": int(torch.cuda.max_memory_reserved(dev)),
+                    "library_scratch": int(_lib.lib().cmf_mem_stats())}
+        peak_mem["total"] = peak_mem["torch_max_allocated"] + peak_mem["library_scratch"]
 
     # BASELINE config 2 (fwd only, eval-mode BN, same batch) timed in the same run: 20 steps behind 3 warm-up steps, the chains back
     # on the stream pool.  Not part of `value`.  (Every rank runs it: no collective inside.)
     config2 = None
-    if a.mode == "train" and a.model == "cmflow" and not a.no_config2:
+    if a.full and a.mode == "train" and a.model == "cmflow" and not a.no_config2:
         from cmflow_amd import fused_blocks as _FB
         _FB.set_serial(net, bool(a.serial))
         net.eval()
@@ -550,7 +635,7 @@ def main():
     # the gradient all-reduce alone (world > 1, or forced at world 1): 20 back-to-back all-reduces of the flat bucket between one
     # event pair on the current stream -- every rank enters them
     allreduce_ms = None
-    if a.mode == "train" and dist.is_initialized() and not one_gpu:
+    if a.full and a.mode == "train" and dist.is_initialized() and not one_gpu:
         bucket = step.bucket.flat if hasattr(step, "bucket") and hasattr(step.bucket, "flat") else None
         if bucket is not None:
             scratch = torch.zeros_like(bucket)
@@ -582,9 +667,9 @@ def main():
                                        "every one costs 0.13-0.18 ms per step); the kernel's own rate is roofline_isolated" % prof["sample_every"]})
             roof.pop("note", None)
         cpu = cpu1 = hbm = None
-        if world == 1 and not a.no_op_rooflines:
+        if a.full and world == 1 and not a.no_op_rooflines:
             hbm = hbm_op_rooflines(dev)
-        if not a.no_cpu_baseline and world == 1:           # the CPU leg is timed at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:           # the CPU leg is timed at N=1 only
             cpu = cpu_baseline(a.mode, a.model)
             # BASELINE config 1 (the reference's own CPU-runnable case): one frame pair, forward, eval mode (main_util.py:142)
             cpu1 = cpu_baseline("fwd", a.model, budget_s=8.0, B=1)
@@ -613,7 +698,7 @@ def main():
             # x3 for fwd+bwd) -- the build's hoisted first convs execute fewer FLOPs than that
             "algorithmic_model_tflops": round(pairs / dt * 25.52e9 * (3.0 if a.mode == "train" else 1.0) / 1e12, 2),
             # ms per step of three back-to-back timed regions of `steps` steps each (the first one is `value`): rank 0's clock
-            "extra": {"ms_per_step_regions": [round(v, 3) for v in spread],
+            "extra": {"ms_per_step_regions": [round(v, 3) for v in spread] if a.full else None,
                       # per-launch durations bracketed inside the timed region: launches on four streams overlap, so their sum exceeds
                       # the wall time -- a concurrency artefact, not a roofline figure
                       "contended_per_launch": ({k: contended[k] for k in ("achieved", "frac", "avg_us", "launches")} if contended else None),
@@ -621,8 +706,10 @@ def main():
                       "peak_mem_bytes": peak_mem, "config2_fwd": config2,
                       "config2_fwd_ms_per_step": config2["ms_per_step"] if config2 else None},
             "ranks_seen": ranks_seen, "devices": devices, "backend": backend, "allreduce_ms": allreduce_ms,
-            "source_id": _lib.source_id(),
+            "source_id": _lib.source_id(), "full": bool(a.full),
         }
+        if dumped is not None:
+            dump_outputs(dumped, a.dump_outputs)
         if a.gemm_table:
             with open(a.gemm_table, "w") as f:
                 f.write(gemm_shape_table(prof, "timed region (chains on the side-stream pool: durations are contended)"))

@@ -1003,7 +1003,7 @@ def test_dense_cloud_train_step_matches_oracle(dev, manifest, golden_dir, args):
 def test_bench_two_ranks_control_flow(dev):
     """bench.py under torch.distributed.run with two ranks (both on cuda:0 over gloo, CMF_BENCH_ONE_GPU=1): every
     collective of the script -- parameter broadcast, the gradient all-reduce inside every step INCLUDING the extra
-    isolated-roofline steps after the timed region, the max-over-ranks of the time -- is entered by both ranks, rank 0
+    isolated-roofline steps of --full after the timed region, the max-over-ranks of the time -- is entered by both ranks, rank 0
     prints exactly one JSON line, and both processes exit cleanly (a rank-0-only training step would hang here)."""
     import json
     import socket
@@ -1015,7 +1015,8 @@ def test_bench_two_ranks_control_flow(dev):
         port = s.getsockname()[1]
     env = dict(os.environ, CMF_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
+           "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1023,6 +1024,44 @@ def test_bench_two_ranks_control_flow(dev):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["config"]["parallelism"] == "dp2" and rec["cpu_baseline"] is None
     assert rec["roofline"] is not None and rec["roofline_isolated"] is not None and rec["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(dev, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints one JSON line with the headline fields and nulls for
+    what only --full measures, and --dump-outputs writes what the last timed training step returned: float32 / float64 arrays,
+    at most 64 MB in all, the same names and shapes in two runs with the same arguments (seeded inputs), the same loss."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["full"] is False
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "frame-pairs/s" and rec["higher_is_better"] is True
+        assert abs(rec["value"] - 4 * 1e3 / rec["ms_per_step"]) <= 1e-2 * rec["value"]
+        assert rec["dtype"] == "f32" and rec["metric"] == "frame-pairs/sec CMFlow fwd+bwd"
+        assert rec["roofline"] is None and rec["roofline_isolated"] is None and rec["roofline_hbm"] is None and rec["cpu_baseline"] is None
+    files = {r: sorted(os.listdir(tmp_path / r)) for r in ("a", "b")}
+    assert files["a"] == files["b"]
+    assert {"loss.npy", "pred_flow.npy", "mseg_pre.npy", "pre_trans.npy", "mask.npy", "grad.npy", "params.npy"} <= set(files["a"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files["a"]) <= 64 * 1000 * 1000
+    arr = {r: {f: np.load(tmp_path / r / f) for f in files[r]} for r in ("a", "b")}
+    for f in files["a"]:
+        a, b = arr["a"][f], arr["b"][f]
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, f
+        assert np.isfinite(a).all(), f
+    assert arr["a"]["pred_flow.npy"].shape == (4, 3, 256)
+    assert arr["a"]["grad.npy"].size > 1000000 and arr["a"]["params.npy"].size >= arr["a"]["grad.npy"].size
+    la, lb = float(arr["a"]["loss.npy"]), float(arr["b"]["loss.npy"])
+    assert abs(la - lb) <= 1e-3 * max(1.0, abs(lb)), (la, lb)
 
 
 def test_two_rank_cmflow_step_matches_single_rank_shards(dev, tmp_path):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B/A/B of the lock-step first encoder (CMF_BODY_BATCH) in one call: training steps, and the first encoder alone
 for b in 0 1 0 1; do
-  CMF_BODY_BATCH=$b python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-op-rooflines 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('train CMF_BODY_BATCH=$b', d['ms_per_step'], d['extra']['ms_per_step_regions'])"
+  CMF_BODY_BATCH=$b python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-op-rooflines 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('train CMF_BODY_BATCH=$b', d['ms_per_step'], d['extra']['ms_per_step_regions'])"
 done
 for b in 0 1; do
   echo "== CMF_BODY_BATCH=$b: first encoder alone (both clouds, forward + backward, isolated kernel durations)"

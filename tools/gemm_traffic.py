@@ -23,7 +23,7 @@ def per_launch(path, counter):
 
 f, nf = per_launch(sys.argv[1], "FETCH_SIZE")
 w, nw = per_launch(sys.argv[2], "WRITE_SIZE")
-out = {"kernel": "gemm_kernel<128,128,...> / <256,128,...> and pgemm_kernel<...> dispatches with >= 256 workgroups, bench.py --steps 3 --warmup 2 (all steps of the run)",
+out = {"kernel": "gemm_kernel<128,128,...> / <256,128,...> and pgemm_kernel<...> dispatches with >= 256 workgroups, bench.py --full --steps 3 --warmup 2 (all steps of the run)",
        "launches": nf, "fetch_bytes_per_launch": round(2.0 * f * 1024 / max(nf, 1)), "write_bytes_per_launch": round(w * 1024 / max(nw, 1)),
        "note": "FETCH_SIZE x 2 (gfx950: 64 B counted per 128-B request), WRITE_SIZE as reported; KB -> bytes"}
 out["source_id"] = _lib.source_id()

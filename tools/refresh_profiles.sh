@@ -1,6 +1,7 @@
 # One gpurun call that regenerates the bench / kernel-stats / overlap / probe files under profiles/ (raw output in gpurun_out/r).
 set -x
 cd $GRAFT_REPO_ROOT
+ROOT=$(pwd)
 R=$GRAFT_REPO_ROOT/gpurun_out/r; mkdir -p $R
 export TMPDIR=/tmp
 # PMC constants first (bench.py reports them only beside matching kernel sources): the in-step GEMM traffic and the drop-in op table
@@ -8,18 +9,18 @@ bash tools/session.sh r pmc_gemm > /dev/null 2>&1
 cp $R/gemm_traffic.json profiles/r06_gemm_traffic_instep.json
 bash tools/session.sh r op_pmc > /dev/null 2>&1
 cp $R/op_hbm_pmc.json profiles/r06_op_hbm_pmc.json
-python bench.py --gemm-table $R/gemm_shapes_train.md > $R/bench_train.json 2> $R/bench_train.err
-python bench.py --mode fwd --gemm-table $R/gemm_shapes_fwd.md > $R/bench_fwd.json 2> $R/bench_fwd.err
-python bench.py --model cmflow_t --no-cpu-baseline --no-op-rooflines > $R/bench_cmflow_t.json 2>/dev/null
-python bench.py --model raflow --no-cpu-baseline --no-op-rooflines > $R/bench_raflow.json 2>/dev/null
-python bench.py --force-allreduce --no-cpu-baseline --no-op-rooflines > $R/bench_forced_allreduce.json 2>/dev/null
+python bench.py --full --gemm-table $R/gemm_shapes_train.md > $R/bench_train.json 2> $R/bench_train.err
+python bench.py --full --mode fwd --gemm-table $R/gemm_shapes_fwd.md > $R/bench_fwd.json 2> $R/bench_fwd.err
+python bench.py --full --model cmflow_t --no-cpu-baseline --no-op-rooflines > $R/bench_cmflow_t.json 2>/dev/null
+python bench.py --full --model raflow --no-cpu-baseline --no-op-rooflines > $R/bench_raflow.json 2>/dev/null
+python bench.py --full --force-allreduce --no-cpu-baseline --no-op-rooflines > $R/bench_forced_allreduce.json 2>/dev/null
 rm -rf /tmp/p1 /tmp/p2 /tmp/p3
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --no-config2 > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --no-config2 > /dev/null 2>&1)
 cp $(find /tmp/p1 -name "*kernel_stats.csv" | head -1) $R/train_kernel_stats.csv
 python tools/trace_overlap.py $(find /tmp/p1 -name "*kernel_trace.csv" | head -1) loss_sample_kernel 5 11 > $R/train_overlap.txt 2>&1
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p2 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --mode fwd > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p2 -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --mode fwd > /dev/null 2>&1)
 cp $(find /tmp/p2 -name "*kernel_stats.csv" | head -1) $R/fwd_kernel_stats.csv
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p3 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --no-config2 --serial > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p3 -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --no-config2 --serial > /dev/null 2>&1)
 cp $(find /tmp/p3 -name "*kernel_stats.csv" | head -1) $R/train_serial_kernel_stats.csv
 for c in 0 1; do echo "== CMF_CHAIN_TRAIN=$c (ENC1_SERIAL=1: isolated kernel durations)"; ENC1_SERIAL=1 CMF_CHAIN_TRAIN=$c python tools/enc1_profile.py 2>&1 | grep -v "Warning\|_warn_once\|amdgpu.ids" | head -22; done > $R/enc1_profile.txt
 python tools/gemm_vendor_compare.py 2>&1 | grep -v amdgpu.ids > $R/gemm_vendor_compare.txt
