@@ -1628,17 +1628,17 @@ static int gemm_diag_rt()
 }
 
 // 256 x 128 tiles for tall interior shapes (env CMF_GEMM_TALL=0: the 128 x 128 tiles everywhere, A/B)
-static int gemm_tall_mode()
+static bool gemm_tall()
 {
-    static const int mode = getenv("CMF_GEMM_TALL") ? atoi(getenv("CMF_GEMM_TALL")) : 1;
-    return mode;
+    static const bool on = !(getenv("CMF_GEMM_TALL") && getenv("CMF_GEMM_TALL")[0] == '0');
+    return on;
 }
 
-// 128 x 256 tiles for the gathering forward GEMM (env CMF_GEMM_WIDE=0: 128 x 128, A/B; 2: also below two workgroups per CU, tests)
-static int gemm_wide_mode()
+// 128 x 256 tiles for the gathering forward GEMM (env CMF_GEMM_WIDE=0: 128 x 128, A/B)
+static bool gemm_wide()
 {
-    static const int mode = getenv("CMF_GEMM_WIDE") ? atoi(getenv("CMF_GEMM_WIDE")) : 1;
-    return mode;
+    static const bool on = !(getenv("CMF_GEMM_WIDE") && getenv("CMF_GEMM_WIDE")[0] == '0');
+    return on;
 }
 
 extern "C" int cmf_gemm(int M, int N, int K, int a_t, int b_t,
@@ -1689,16 +1689,16 @@ extern "C" int cmf_gemm(int M, int N, int K, int a_t, int b_t,
     const int kind = epilogue_kind(g);
     // 256 x 128 tiles (wave tile 128 x 64, 2 workgroups per CU): half the operand bytes per flop through L2 and LDS-direct, a quarter
     // fewer LDS fragment reads, tiles twice as long against the same prologue / epilogue (round 5; tools/lab/gemm_lab.hip: + 5-20 % on the
-    // model's plain shapes).  Interior shapes only (the LDS-direct loop); enough tiles to fill 2 workgroups per CU.
-    const int tall_mode = gemm_tall_mode();
+    // model's plain shapes).  Interior shapes only (the LDS-direct loop); enough tiles to fill 2 workgroups per CU.  Not for the
+    // transposed-A layouts (the weight gradients: worse at the split counts that fill the chip, round 5).
     const long long work_tiles = (long long)(M / 256) * ((N + 127) / 128) * g.split_k;
-#define CMF_PICK(AT, BT, EP)                                                                               \
-    (big ? launch<256, 128, AT, BT, EP>(g, st) :                                                          \
-     tall ? (wide ? launch<128, 128, AT, BT, EP>(g, st) : launch<128, 64, AT, BT, EP>(g, st)) \
+#define CMF_PICK_128(AT, BT, EP)                                                                  \
+    (tall ? (wide ? launch<128, 128, AT, BT, EP>(g, st) : launch<128, 64, AT, BT, EP>(g, st)) \
           : (wide ? launch<64, 128, AT, BT, EP>(g, st) : launch<64, 64, AT, BT, EP>(g, st)))
+#define CMF_PICK(AT, BT, EP) (big ? launch<256, 128, AT, BT, EP>(g, st) : CMF_PICK_128(AT, BT, EP))
     const int pgrid = thin_done ? 0 : cmf_pgemm_grid(g, a_t, b_t, kind);
     if (!pgrid && staged_dw) g.no_direct = 1;
-    const bool big = tall_mode && (!a_t || tall_mode == 3) && M % 256 == 0 && N % 128 == 0 && K % G_BK == 0 && work_tiles >= 384 && !g.no_direct && !(accumulate && g.split_k == 1);
+    const bool big = gemm_tall() && !a_t && M % 256 == 0 && N % 128 == 0 && K % G_BK == 0 && work_tiles >= 384 && !g.no_direct && !(accumulate && g.split_k == 1);
     if (thin_done)         err = 0;
     else if (pgrid) {
         const long long pe = gprof_open(2.0 * M * N * K, st, &g, (a_t ? 2 : 0) | (b_t ? 1 : 0) | 4, 128, 128);      // layout bit 2: persistent kernel
@@ -1709,9 +1709,10 @@ extern "C" int cmf_gemm(int M, int N, int K, int a_t, int b_t,
     else if (!a_t && b_t)  err = kind == 1 ? CMF_PICK(false, true, 1) : CMF_PICK(false, true, 0);
     else if (!a_t && !b_t) err = kind == 2 ? CMF_PICK(false, false, 2) : kind == 3 ? CMF_PICK(false, false, 3) :
                                  kind == 4 ? CMF_PICK(false, false, 4) : kind == 5 ? CMF_PICK(false, false, 5) : CMF_PICK(false, false, 0);
-    else if (a_t && !b_t)  err = CMF_PICK(true, false, 0);
-    else                   err = CMF_PICK(true, true, 0);
+    else if (a_t && !b_t)  err = CMF_PICK_128(true, false, 0);
+    else                   err = CMF_PICK_128(true, true, 0);
 #undef CMF_PICK
+#undef CMF_PICK_128
     if (err) return err;
     if (split_k > 1) return cmf_splitk_reduce(M, N, g.split_k, workspace, C, ldc, accumulate, st);     // (the persistent kernel may have lowered it)
     return 0;
@@ -1739,12 +1740,10 @@ extern "C" int cmf_gemm_gather_affine(int M, int N, int K, const float *Y, long 
     g.stats = stats;                                    // train mode: [M / 128][2][N] partial sums of the output
     g.diag = gemm_diag_rt();
     // (256 x 128 tiles measured here, round 5: 111 against 118 TF -- the per-row state of the gathering loads and the fragment prologue
-    //  do not fit 256 registers beside a 128 x 64 wave tile; CMF_GEMM_TALL=2 keeps that form reachable)
-    if (gemm_tall_mode() == 2 && M % 256 == 0 && (long long)(M / 256) * (N / 128) >= 384)
-        return stats ? launch<256, 128, false, true, 1, 1>(g, st) : launch<256, 128, false, true, 0, 1>(g, st);
+    //  do not fit 256 registers beside a 128 x 64 wave tile)
     // 128 x 256 tiles (wave tile 64 x 128): the fragment arithmetic of the gathered operand -- 16 elements per lane and chunk either
     // way -- then sits beside 64 MFMAs instead of 32, and a row panel is gathered once for 256 output columns
-    if (gemm_wide_mode() && N % 256 == 0 && ((long long)(M / 128) * (N / 256) >= 512 || gemm_wide_mode() == 2))
+    if (gemm_wide() && N % 256 == 0 && (long long)(M / 128) * (N / 256) >= 512)
         return stats ? launch<128, 256, false, true, 1, 1>(g, st) : launch<128, 256, false, true, 0, 1>(g, st);
     return stats ? launch<128, 128, false, true, 1, 1>(g, st) : launch<128, 128, false, true, 0, 1>(g, st);
 }
@@ -1802,8 +1801,7 @@ extern "C" int cmf_gemm_dx_gather_sum(int M, int cin, int cout, const float *dZ,
     g_dxsum_points_hint = 0;                            // (a hint serves one call)
     g.diag = gemm_diag_rt();
     // (256-row tiles -- wave tile 128 x 64 = two 64-row ranges of `pieces` -- measured here, round 5: 99.7 against 105 TF at 524288 rows:
-    //  the serial row walk of the epilogue doubles per wave while only two workgroups per CU are left to cover it; CMF_GEMM_TALL=2: A/B)
-    if (gemm_tall_mode() == 2 && M % 256 == 0 && (long long)(M / 256) * (cin / 128) >= 384) return launch<256, 128, false, false, 4, 4>(g, st);
+    //  the serial row walk of the epilogue doubles per wave while only two workgroups per CU are left to cover it)
     return launch<128, 128, false, false, 4, 4>(g, st);
 }
 
@@ -1811,7 +1809,7 @@ extern "C" int cmf_gemm_dx_gather_sum(int M, int cin, int cout, const float *dZ,
 // dealt to the 8 XCDs); 0 = no preference (shape not tileable that way, or CMF_GEMM_TALL=0): the caller's usual choice.
 extern "C" int cmf_gemm_dw_gather_split(int cout, int cin, long long nrows)
 {
-    if (!gemm_tall_mode() || cout <= 0 || cin <= 0 || cout % 256 || cin % 128 || nrows % G_BK) return 0;
+    if (!gemm_tall() || cout <= 0 || cin <= 0 || cout % 256 || cin % 128 || nrows % G_BK) return 0;
     const long long tiles = (long long)(cout / 256) * (cin / 128), chunks = nrows / G_BK;
     int s = (int)(512 / tiles) / 8 * 8;
     while (s >= 8 && chunks / s < 8) s -= 8;
@@ -1848,7 +1846,7 @@ extern "C" int cmf_gemm_dw_gather(int cout, int cin, long long nrows, const floa
 }
 
 // cmf_gemm_dw_gather with the train-mode BatchNorm backward of the output gradient formed while the A operand is staged (the bnb_*
-// path of cmf_gemm_dw_bn_bwd) -- BOTH operands of the second encoder's largest weight gradient are then formed in the staging loop:
+// path of the kernel) -- BOTH operands of the second encoder's largest weight gradient are then formed in the staging loop:
 //   dZ = al * dU + be * (Z - mean) + ga   (written to dZ_out for the data-gradient GEMM),   B = relu(prob (Y[rows] + wx3 . dxyz))
 // and the stand-alone cmf_bn_bwd_apply pass over (rows, cout) -- read dU, read Z, write dZ -- disappears.  Same operations in the same
 // order as cmf_bn_bwd_apply followed by cmf_gemm_dw_gather: bit-identical results.
@@ -1873,38 +1871,6 @@ extern "C" int cmf_gemm_dw_gather_bn_bwd(int cout, int cin, long long nrows, con
     g.bnb_ic = (float)(1.0 / (double)nrows); g.bnb_out = dZ_out; g.ldbo = ldo;
     const bool tall = split_k > 1 && split_k == cmf_gemm_dw_gather_split(cout, cin, nrows);
     const int err = tall ? launch<256, 128, true, false, 0, 2>(g, st) : launch<128, 128, true, false, 0, 2>(g, st);
-    if (err) return err;
-    if (split_k > 1) return cmf_splitk_reduce(cout, cin, split_k, workspace, dW, lddw, accumulate, st);
-    return 0;
-}
-
-// Weight gradient of a layer whose output gradient still has to go through the train-mode BatchNorm backward:
-//   dZ = al * dU + be * (Z - mean) + ga  (cmf_common.h cmf_bnb_coef of a / mean / invstd / sums, 1 / rows),   dW (+)= dZ^T @ act(X)
-// formed while the A operand is staged -- the stand-alone cmf_bn_bwd_apply pass (read dU, read Z, write dZ) disappears and dZ
-// is written to dZ_out (a buffer of its own: other workgroups still read dU) as a by-product for the data-gradient GEMM that
-// follows.  Same operations as cmf_bn_bwd_apply + cmf_gemm(a_t = 1, b_t = 0) on the register-staged loop: bit-identical
-// results.  cout, cin multiples of 128, rows a multiple of 16; X activated by (prob_a, prob_c) or as stored (both NULL).
-extern "C" int cmf_gemm_dw_bn_bwd(int cout, int cin, long long rows, const float *dU, long long ldu, const float *Z, long long ldz,
-                                  const float *a, const float *mean, const float *invstd, const float *sums, float *dZ_out, long long ldo,
-                                  const float *X, long long ldx, const float *prob_a, const float *prob_c,
-                                  float *dW, long long lddw, int split_k, float *workspace, int accumulate, void *stream)
-{
-    CMF_CHECK_ARG(cout > 0 && cin > 0 && rows > 0 && rows < (1ll << 31) && split_k >= 1);
-    CMF_CHECK_ARG(cout % 128 == 0 && cin % 128 == 0 && rows % G_BK == 0);
-    CMF_CHECK_ARG(dU && Z && a && mean && invstd && sums && X && dW && (split_k == 1 || workspace));
-    CMF_CHECK_ARG(ldu % 4 == 0 && ldz % 4 == 0 && ldx % 4 == 0 && (!dZ_out || ldo % 4 == 0));
-    CMF_CHECK_ARG((((uintptr_t)dU | (uintptr_t)Z | (uintptr_t)X | (uintptr_t)dZ_out) & 15) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    GemmArgs g{};
-    g.M = cout; g.N = cin; g.K = (int)rows; g.A = dU; g.lda = ldu; g.B = X; g.ldb = ldx;
-    g.C = split_k > 1 ? workspace : dW; g.ldc = split_k > 1 ? cin : lddw;
-    g.prob_a = prob_a; g.prob_c = prob_c; g.split_k = split_k; g.accumulate = split_k > 1 ? 0 : accumulate;
-    g.bnb_z = Z; g.ldbz = ldz; g.bnb_a = a; g.bnb_mean = mean; g.bnb_invstd = invstd; g.bnb_sums = sums;
-    g.bnb_ic = (float)(1.0 / (double)rows); g.bnb_out = dZ_out; g.ldbo = ldo;
-    g.no_direct = 1;
-    static const int diag_rt = getenv("CMF_GEMM_DIAG_RT") ? atoi(getenv("CMF_GEMM_DIAG_RT")) : 0;
-    g.diag = diag_rt;
-    const int err = launch<128, 128, true, false, 0>(g, st);
     if (err) return err;
     if (split_k > 1) return cmf_splitk_reduce(cout, cin, split_k, workspace, dW, lddw, accumulate, st);
     return 0;

@@ -21,21 +21,17 @@ namespace {
 
 // training through the register chain (csrc/setconv_chain.hip): the narrow block's slot-level activations z1 / z2 / z3 are never stored
 // -- every pass recomputes them from the gathered per-point rows; z3's slot of `saved` holds the selected pre-activations (P x C3).
-// OPT-IN (CMF_CHAIN_TRAIN=1), measured round 5 on the training step's first encoder (both clouds, four scales, isolated kernel
-// time): five chain passes 1.64 ms against 1.50 ms for the per-layer kernels they replace -- at 64 K .. 512 K rows per launch the
-// passes' fixed costs (constants and weights into LDS per workgroup, a statistics row per wave, the re-gather per pass) eat what
-// the 3x lower HBM traffic saves; the step is equal within noise (20.15 vs 20.20 ms).  Inference (one pass, nothing else to
-// amortise) is where the chain pays: forward 5.91 -> 5.56 ms.
-// With eval-mode BatchNorm and a backward pass to follow (the regime of every epoch after the first in the reference's loop: no
-// statistics passes) the chain is three passes against seven per-layer kernels -- 1.25 against 1.50 ms -- and is the DEFAULT there
-// (CMF_CHAIN_TRAIN=0: the per-layer kernels everywhere).
+// Eval-mode BatchNorm with a backward pass to follow only (the regime of every epoch after the first in the reference's loop: no
+// statistics passes): three passes against seven per-layer kernels -- 1.25 against 1.50 ms.  [With train-mode BN (round 5, removed)
+// the two statistics passes made it five chain passes at 1.64 ms against 1.50 ms for the per-layer kernels: at 64 K .. 512 K rows
+// per launch the passes' fixed costs (constants and weights into LDS per workgroup, a statistics row per wave, the re-gather per
+// pass) ate what the 3x lower HBM traffic saved.]  Inference (one pass, cmf_setconv_chain_infer) is where the chain pays most:
+// forward 5.91 -> 5.56 ms.
 inline bool chain_train(const cmf_setconv_desc *d)
 {
-    static const int mode = getenv("CMF_CHAIN_TRAIN") ? atoi(getenv("CMF_CHAIN_TRAIN")) : -1;     // -1: eval-mode BN only, 0: never, 1: always
-    const bool on = mode == 1 || (mode == -1 && !d->training);
     const long long M = (long long)d->B * d->N * d->S;
-    return on && !d->inference && cmf_setconv_chain_supported(d->N, d->S, d->O1, d->C[0], d->C[1], M) && M % 128 == 0 && d->ldy % 4 == 0 &&
-           ((uintptr_t)d->y & 15) == 0;
+    return !d->training && !d->inference && cmf_setconv_chain_supported(d->N, d->S, d->O1, d->C[0], d->C[1], M) && M % 128 == 0 &&
+           d->ldy % 4 == 0 && ((uintptr_t)d->y & 15) == 0;
 }
 
 struct Bump {
@@ -91,26 +87,13 @@ struct Layout {
     float *bn[6];                 // per layer: mean | invstd | a | c   (4 * C_l)
     // scratch
     float *partial, *partial_x, *sums, *t6, *t5, *t4, *dx, *dU3, *dU2, *dU1, *splitk;
-    float *dZ2;                   // dZ of BN layer 1, written by the weight-gradient GEMM that fuses its BN backward (or null)
+    float *dZ2;                   // dZ of BN layer 1, written by the gathering weight-gradient GEMM that fuses its BN backward (or null)
     size_t saved_floats, scratch_floats;
 };
 
 inline int chan(const cmf_setconv_desc *d, int layer)       // out channels of BN layer 0..5
 {
     return layer == 0 ? d->O1 : d->C[layer - 1];
-}
-
-// The wide backward layer (cout <- cin over `rows`) may fuse its BN backward into the weight-gradient GEMM
-// (cmf_gemm_dw_bn_bwd): shapes the fused kernel takes, and long enough that the unfused cmf_gemm would run the same
-// register-staged loop (K >= 32768, gemm.hip) -- the two forms are then bit-identical.  Opt-in (CMF_BNB_FUSED=1), measured
-// in four same-box A/B pairs of the training step: the stand-alone pass (0.48 ms per step) goes, the four weight-gradient
-// GEMMs that absorb it run 99.5 instead of 112 TF (+0.27 ms; two more operand loads per thread and chunk in the staging
-// loop) -- 21.33-21.43 against 21.42-21.53 ms per step, i.e. 0.1 ms, for a tiled kernel that is 2 points further from its
-// MFMA roof.  Not worth a second form of the layer as the default.
-inline bool bnb_fusable(long long rows, int cout, int cin)
-{
-    static const bool on = getenv("CMF_BNB_FUSED") && getenv("CMF_BNB_FUSED")[0] == '1';
-    return on && cout % 128 == 0 && cin % 128 == 0 && rows % 16 == 0 && rows >= 32768 && rows < (1ll << 31);
 }
 
 // The arenas are sized by PATH (VERDICT r5 item 7 / ADVICE r4).  A block that never materialises its grouped first-layer tensor
@@ -139,8 +122,8 @@ inline bool gather_sum_layout(const cmf_setconv_desc *d)
 // pass over (M, C2) -- read dU, read Z, write dZ: 3 GB per step at B = 64 -- goes, dZ lands in a buffer of its own for the data-gradient
 // GEMM (other column tiles of the slab still read dU).  Bit-identical to the two-kernel form.  [measured, round 6, A/B/A/B on one box:
 // 18.999 / 19.035 -> 18.809 / 18.844 ms per step; the four GEMMs that absorb the pass run 2 points further from their MFMA roof --
-// isolated cmf_gemm 0.739 -> 0.719 -- which is what the round-3 form of this fusion (CMF_BNB_FUSED, non-gathering) was left opt-in for:
-// the step is the figure of merit.]  CMF_BNB_GATHER=0: the stand-alone pass (A/B).
+// isolated cmf_gemm 0.739 -> 0.719 -- which is what the round-3 form of this fusion (non-gathering, 0.1 ms per step: since removed) was
+// left opt-in for: the step is the figure of merit.]  CMF_BNB_GATHER=0: the stand-alone pass (A/B).
 inline bool bnb_gather(const cmf_setconv_desc *d)
 {
     static const bool on = !(getenv("CMF_BNB_GATHER") && getenv("CMF_BNB_GATHER")[0] == '0');
@@ -184,7 +167,7 @@ Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool
         L.dU2 = t.take(M * C2);
         // (summed inside the GEMM: pieces (P + M/64) x O1 | perm M | source points M | relative coordinates 4 M -- sum_slots below)
         L.dU1 = t.take(gather_sum_layout(d) ? (size_t)(P + M / 64) * O1 + 6 * (size_t)M : (size_t)M * O1);
-        L.dZ2 = (d->training && (bnb_fusable(M, C2, O1) || bnb_gather(d))) ? t.take(M * C2) : nullptr;
+        L.dZ2 = bnb_gather(d) ? t.take(M * C2) : nullptr;
         size_t sk = 0;
         sk = std::max(sk, (size_t)dw_split(P, C6, C5) * C6 * C5);
         sk = std::max(sk, (size_t)dw_split(P, C5, C4) * C5 * C4);
@@ -210,14 +193,14 @@ Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool
 #define CMF_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
 
 }  // namespace
-// csrc/setconv_chain.hip (internal): the narrow block's neighbour-slot layers as register-chain passes
-// (mode: 0 inference, 1 / 2 statistics of z2 / z3, 3 max over the ball + argmax + selected pre-activations, 4 / 5 backward of layers 3 / 2)
+// csrc/setconv_chain.hip (internal): the narrow block's neighbour-slot layers as register-chain passes with eval-mode BN
+// (mode: 0 inference, 1 max over the ball + argmax + selected pre-activations, 2 / 3 backward of layers 3 / 2)
 bool cmf_setconv_chain_supported(int N, int S, int O1, int C2, int C3, long long M);
 long long cmf_setconv_chain_waves(long long M, int backward);
-int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *dxyz, const float *y, long long ldy, const float *wx,
+int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
                            long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
-                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *sums,
-                           const float *dU_in, float *dU_out, float *slabs, void *stream);
+                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *dU_in, float *dU_out,
+                           float *slabs, void *stream);
 // csrc/pointwise.hip (internal)
 int cmf_bn_relu_maxpool_sel(long long P, int S, int C, const float *z, const float *a, const float *c, float *out, long long ldo,
                             unsigned char *argmax, float *zsel, void *stream);
@@ -323,8 +306,7 @@ int dx_gemm(const cmf_setconv_desc *d, const Layout &L, long long rows, int cout
 // Narrow layers run the fused single-pass kernel (cmf_thin_bwd_layer: dZ is never stored); the wide ones of the second
 // encoder the BN backward in place followed by the two tiled GEMMs.  CMF_THIN_FUSED=0 forces the three-kernel form.
 int bwd_layer(const cmf_setconv_desc *d, const Layout &L, int l_out, long long rows, int cout, int cin, float *dU, const float *z_out,
-              const float *w, const float *x, int l_in, float *dU_in, const float *dxyz, float *dw, int acc_w, void *st,
-              float *dz_buf = nullptr)
+              const float *w, const float *x, int l_in, float *dU_in, const float *dxyz, float *dw, int acc_w, void *st)
 {
     const float *b = L.bn[l_out];
     if (d->acc_bn[l_out]) CMF_TRY(cmf_colsum_finalize(tiles128(rows), cout, L.partial, L.sums, d->dbeta[l_out], d->dgamma[l_out], st));
@@ -336,14 +318,6 @@ int bwd_layer(const cmf_setconv_desc *d, const Layout &L, int l_out, long long r
         return cmf_thin_bwd_layer(rows, cout, cin, dU, cout, z_out, cout, b + 2 * cout, b, b + cout, d->training ? L.sums : nullptr,
                                   w, cin, x, cin, l_in >= 0 ? 1 : 0, bi ? bi + 2 * ci : nullptr, bi ? bi + 3 * ci : nullptr, bi,
                                   bi ? bi + ci : nullptr, dxyz, dU_in, cin, l_in >= 0 ? L.partial : nullptr, dw, cin, acc_w, L.splitk, st);
-    }
-    if (dz_buf && dw && d->training && l_in >= 0 && bnb_fusable(rows, cout, cin)) {
-        // BN backward inside the weight-gradient GEMM's operand staging; dZ lands in dz_buf for the data-gradient GEMM
-        const float *bi = L.bn[l_in];
-        const int ci = chan(d, l_in), split = dw_split(rows, cout, cin);
-        CMF_TRY(cmf_gemm_dw_bn_bwd(cout, cin, rows, dU, cout, z_out, cout, b + 2 * cout, b, b + cout, L.sums, dz_buf, cout, x, cin,
-                                   bi + 2 * ci, bi + 3 * ci, dw, cin, split, split > 1 ? L.splitk : nullptr, acc_w, st));
-        return dx_gemm(d, L, rows, cout, cin, dz_buf, w, x, l_in, dU_in, dxyz, st);
     }
     CMF_TRY(cmf_bn_bwd_apply(rows, cout, dU, z_out, cout, b + 2 * cout, b, b + cout, d->training ? L.sums : nullptr, st));
     CMF_TRY(dw_gemm(d, L, rows, cout, cin, dU, x, l_in, dw, acc_w, st));
@@ -455,34 +429,14 @@ static int setconv_forward_part(const cmf_setconv_desc *d, void *st, int part)
         return cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, st);
     }
     if (chain_train(d)) {
-        // training (batch statistics: a pass per BatchNorm layer, each recomputing the layers below it) or eval-mode BN with a backward
-        // pass to follow (one pass): nothing but the pooled rows, their argmax slots and the selected pre-activations is stored
-        const int wv = (int)cmf_setconv_chain_waves(M, 0);
-        auto pass = [&](int mode) {
-            return cmf_setconv_chain_pass(mode, M, d->N, d->S, L.idx, d->xyz, d->training ? L.dxyz : nullptr, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0],
-                                          d->w[1], L.x, C3, L.z3, L.argmax, L.partial, nullptr, nullptr, nullptr, nullptr, nullptr, st);
-        };
-        if (d->training) {
-            CMF_TRY(cmf_group_affine(d->B, d->N, d->N, d->S, O1, d->y, (int)d->ldy, nullptr, 0, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, 0,
-                                     nullptr, L.dxyz, L.partial, L.partial_x, st));
-            CMF_TRY(cmf_colsum(tiles128(M), 3 * O1 + 4, L.partial_x, L.fwd_sums, 0, nullptr, nullptr, st));
-            CMF_TRY(fold(d, L, 0, M, st));
-            for (int l = 1; l <= 2; ++l) {
-                CMF_TRY(pass(l));
-                const int C = chan(d, l);
-                float *b = L.bn[l];
-                CMF_TRY(cmf_bn_finalize(wv, C, (double)M, L.partial, d->gamma[l], d->beta[l], d->eps[l], d->momentum[l], d->rmean[l], d->rvar[l],
-                                        b, b + C, b + 2 * C, b + 3 * C, d->nbt[l], st));
-            }
-        }
-        CMF_TRY(pass(3));
+        // eval-mode BN with a backward pass to follow (one pass): nothing but the pooled rows, their argmax slots and the selected
+        // pre-activations is stored
+        CMF_TRY(cmf_setconv_chain_pass(1, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0],
+                                       d->w[1], L.x, C3, L.z3, L.argmax, L.partial, nullptr, nullptr, nullptr, nullptr, st));
         if (part == 1) return 0;
         CMF_TRY(fwd_gemm(d, L, P, C3, C4, L.x, -1, d->w[2], L.z4, st));
-        CMF_TRY(fold(d, L, 3, P, st));
         CMF_TRY(fwd_gemm(d, L, P, C4, C5, L.z4, 3, d->w[3], L.z5, st));
-        CMF_TRY(fold(d, L, 4, P, st));
         CMF_TRY(fwd_gemm(d, L, P, C5, C6, L.z5, 4, d->w[4], L.z6, st));
-        CMF_TRY(fold(d, L, 5, P, st));
         return cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, st);
     }
     const bool gather = !d->training && ((d->inference && M % 128 == 0 && C2 % 128 == 0 && O1 % 16 == 0 && d->ldy % 4 == 0 &&
@@ -748,13 +702,13 @@ static int setconv_backward_part(const cmf_setconv_desc *d, void *st, int part)
         CMF_TRY(cmf_maxpool_bwd_point_sel(P, C3, L.dx, C3, L.z3, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, g, L.partial, st));
         if (d->acc_bn[2]) CMF_TRY(cmf_colsum_finalize(tiles128(P), C3, L.partial, L.sums, d->dbeta[2], d->dgamma[2], st));
         else CMF_TRY(cmf_colsum_store(tiles128(P), 2 * C3, L.partial, L.sums, C3, d->dbeta[2], d->dgamma[2], st));
-        CMF_TRY(cmf_setconv_chain_pass(4, M, d->N, d->S, L.idx, d->xyz, d->training ? L.dxyz : nullptr, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
-                                       nullptr, 0, nullptr, L.argmax, L.partial, g, d->training ? L.sums : nullptr, nullptr, L.dU2, L.splitk, st));
+        CMF_TRY(cmf_setconv_chain_pass(2, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
+                                       nullptr, 0, nullptr, L.argmax, L.partial, g, nullptr, L.dU2, L.splitk, st));
         if (d->dw[1]) CMF_TRY(cmf_splitk_reduce(C3, C2, nslab, L.splitk, d->dw[1], C2, d->acc_w[1], (hipStream_t)st));
         if (d->acc_bn[1]) CMF_TRY(cmf_colsum_finalize(wv, C2, L.partial, L.sums, d->dbeta[1], d->dgamma[1], st));
         else CMF_TRY(cmf_colsum_store(wv, 2 * C2, L.partial, L.sums, C2, d->dbeta[1], d->dgamma[1], st));
-        CMF_TRY(cmf_setconv_chain_pass(5, M, d->N, d->S, L.idx, d->xyz, d->training ? L.dxyz : nullptr, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
-                                       nullptr, 0, nullptr, nullptr, L.partial, nullptr, d->training ? L.sums : nullptr, L.dU2, L.dU1, L.splitk, st));
+        CMF_TRY(cmf_setconv_chain_pass(3, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
+                                       nullptr, 0, nullptr, nullptr, L.partial, nullptr, L.dU2, L.dU1, L.splitk, st));
         if (d->dw[0]) CMF_TRY(cmf_splitk_reduce(C2, O1, nslab, L.splitk, d->dw[0], O1, d->acc_w[0], (hipStream_t)st));
     } else
     if (fused && cmf_thin_bwd_supported(C3, C2) && M % 128 == 0 && C3 % 32 == 0 && C2 % 32 == 0 && d->dw[1]) {
@@ -786,7 +740,7 @@ static int setconv_backward_part(const cmf_setconv_desc *d, void *st, int part)
     if (chain) {}
     else if (train_gather(d)) CMF_TRY(bwd_layer1_gather(d, L, M, C2, O1, st));
     else
-    CMF_TRY(bwd_layer(d, L, 1, M, C2, O1, L.dU2, L.z2, d->w[0], L.z1, 0, L.dU1, L.dxyz, d->dw[0], d->acc_w[0], st, L.dZ2));
+    CMF_TRY(bwd_layer(d, L, 1, M, C2, O1, L.dU2, L.z2, d->w[0], L.z1, 0, L.dU1, L.dxyz, d->dw[0], d->acc_w[0], st));
     // first layer: sums {s1,s2,q0,q1,q2}; dgamma/dbeta; dW_xyz from sums; BN backward folded into the scatter
     const float *b0 = L.bn[0];
     const int rows0 = chain ? (int)cmf_setconv_chain_waves(M, 1) : tiles128(M);      // statistics rows of the pass that formed dU1
@@ -933,7 +887,7 @@ static bool body_batchable(int n, const cmf_setconv_desc *descs)
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
         const long long M = (long long)d.B * d.N * d.S;
-        if (!d.training || d.inference || !d.idx_ready || chain_train(&d) || train_gather(&d)) return false;
+        if (!d.training || d.inference || !d.idx_ready || train_gather(&d)) return false;
         if (d.O1 != descs[0].O1 || d.C[0] != descs[0].C[0] || d.C[1] != descs[0].C[1]) return false;
         if (d.O1 > 64 || d.O1 % 32 || d.C[0] > 64 || d.C[0] % 32 || d.C[1] > 64 || d.C[1] % 32) return false;
         if (M % 128 || M >= (1ll << 31) || d.ldy % 4 || ((uintptr_t)d.y & 15)) return false;

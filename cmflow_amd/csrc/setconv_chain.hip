@@ -22,20 +22,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// MODE of the chain kernel
-//   CH_INFER  folded BatchNorm: layers 1-3 + max over the ball -> out                         (inference)
-//   CH_STATS2 layers 1-2: column (sum, sum of squares) of z2 per wave -> partial              (training, pass 2)
-//   CH_STATS3 layers 1-3: the same of z3                                                       (training, pass 3)
-//   CH_POOL   layers 1-3 + max over the ball -> out, the first maximum's slot (argmax) and its raw z3 (zsel)   (training, pass 4)
-//   CH_BWD3   layers 1-3 recomputed; dz3 from the pooled gradient; dW3 slabs; dU2 = mask(dz3 W3) with its BN-backward sums
+// MODE of the chain kernel (every mode with folded, eval-mode BatchNorm)
+//   CH_INFER  layers 1-3 + max over the ball -> out                                                           (inference)
+//   CH_POOL   layers 1-3 + max over the ball -> out, the first maximum's slot (argmax) and its raw z3 (zsel)   (training, forward)
+//   CH_BWD3   layers 1-2 recomputed; dz3 from the pooled gradient; dW3 slabs; dU2 = mask(dz3 W3) with its BN-backward sums
 //   CH_BWD2   layers 1-2 recomputed; dz2 from dU2; dW2 slabs; dU1 = mask(dz2 W2) with its BN-backward and dxyz sums
-enum { CH_INFER = 0, CH_STATS2 = 1, CH_STATS3 = 2, CH_POOL = 3, CH_BWD3 = 4, CH_BWD2 = 5 };
+enum { CH_INFER = 0, CH_POOL = 1, CH_BWD3 = 2, CH_BWD2 = 3 };
 
 struct ChainArgs {
     long long M;                 // neighbour rows = B * N * S
     int N, S, lgS;               // points per sample, slots per point (4 / 8 / 16 / 32) and its log2
     int blocks_per_wave;
-    const float *dxyz;           // (M, 4) relative coordinates of every slot (cmf_group_affine's by-product), or NULL: formed from xyz
     const int *idx;              // (M) source point of every slot, inside its sample
     const float *xyz;            // (B, N, 3)
     const float *y; long long ldy;      // (B * N, 32) per-point rows of the hoisted first conv
@@ -44,10 +41,8 @@ struct ChainArgs {
     const float *w2, *w3;        // (32, 32), (64, 32) dense
     float *out; long long ldo;   // (B * N, 64): max over the ball of relu(bn(z3))
     float *zsel; unsigned char *argmax;          // CH_POOL: (B * N, 64) each
-    float *partial;              // statistics rows, one per WAVE: [2][32] (CH_STATS2, CH_BWD3), [2][64] (CH_STATS3), [5][32] (CH_BWD2)
+    float *partial;              // statistics rows, one per WAVE: [2][32] (CH_BWD3), [5][32] (CH_BWD2)
     const float *g;              // CH_BWD3: (B * N, 64) pooled gradient, already masked by the ReLU at the argmax (cmf_maxpool_bwd_point)
-    const float *sums;           // BN-backward sums (s1 | s2) of the layer being differentiated, or NULL (eval-mode BN: dZ = a dU)
-    float inv_count;             // 1 / M
     const float *dU_in;          // CH_BWD2: dU2 (M, 32)
     float *dU_out;               // CH_BWD3: dU2, CH_BWD2: dU1 (M, 32)
     float *slabs;                // weight-gradient slabs, one per WORKGROUP: [64][32] (CH_BWD3), [32][32] (CH_BWD2)
@@ -75,10 +70,9 @@ __device__ __forceinline__ float ch_group_max(float v, int S)
 }
 __device__ __forceinline__ int ch_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }     // channel of accumulator register r in lane half h
 
-// LDS image (floats).  Constants: the three BN blocks as loaded (bn0 at 0, bn1 at 128, bn2 at 256: mean | invstd | a | c), the
-// coordinate planes wx[d][32] at 512, the backward coefficients ko[4][64] at 608 (a | mean | invstd * s2 / M | s1 / M of the layer
-// being differentiated).  Backward modes add the weights (pitch 33) and a transposition tile per wave.
-constexpr int CH_BN0 = 0, CH_BN1 = 128, CH_BN2 = 256, CH_WX = 512, CH_KO = 608, CH_CONST = 864;
+// LDS image (floats).  Constants: the three BN blocks as loaded (bn0 at 0, bn1 at 128, bn2 at 256: mean | invstd | a | c) and the
+// coordinate planes wx[d][32] at 512.  Then the weights (pitch 33); backward modes add a transposition tile per wave.
+constexpr int CH_BN0 = 0, CH_BN1 = 128, CH_BN2 = 256, CH_WX = 512, CH_CONST = 608;
 constexpr int CH_W2S = CH_CONST, CH_W3S = CH_W2S + 32 * CH_LDW, CH_TT = CH_W3S + 64 * CH_LDW;     // weights, then 4 x (96 x 33) tiles
 constexpr int CH_TILE = 96 * CH_LDW;
 constexpr int CH_LDS_FWD = CH_TT, CH_LDS_BWD = CH_TT + 4 * CH_TILE;
@@ -87,35 +81,23 @@ template <int MODE>
 __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int bx)
 {
     constexpr bool BWD = MODE == CH_BWD3 || MODE == CH_BWD2;
-    constexpr bool L3 = MODE == CH_INFER || MODE == CH_STATS3 || MODE == CH_POOL || MODE == CH_BWD3;      // third layer evaluated
+    constexpr bool L3 = MODE == CH_INFER || MODE == CH_POOL;      // third layer evaluated (CH_BWD3 needs its weights only)
     extern __shared__ __attribute__((aligned(16))) float cst[];
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int S = p.S, lgS = p.lgS;
-    for (int i = tid; i < CH_KO; i += CH_THREADS) {
+    for (int i = tid; i < CH_CONST; i += CH_THREADS) {
         float v;
         if (i < 128) v = p.bn0[i]; else if (i < 256) v = p.bn1[i - 128]; else if (i < 512) v = p.bn2[i - 256];
         else { const int q = i - 512; v = p.wx[(long long)(q & 31) * p.ldwx + (q >> 5)]; }      // plane d of channel ch: wx[ch][d]
         cst[i] = v;
     }
-    if (BWD) {
-        // coefficients of dZ = a (dU - s1/M - (z - mean) invstd s2/M) for the layer being differentiated (thin_bwd_layer's form)
-        const int C = MODE == CH_BWD3 ? 64 : 32;
-        const float *bn = MODE == CH_BWD3 ? p.bn2 : p.bn1;
-        for (int n = tid; n < C; n += CH_THREADS) {
-            const bool train = p.sums != nullptr;
-            cst[CH_KO + n] = bn[2 * C + n];
-            cst[CH_KO + 64 + n] = train ? bn[n] : 0.f;
-            cst[CH_KO + 128 + n] = train ? bn[C + n] * (p.sums[C + n] * p.inv_count) : 0.f;
-            cst[CH_KO + 192 + n] = train ? p.sums[n] * p.inv_count : 0.f;
-        }
-    }
     // the weights live in LDS at an odd pitch (A operands are read per MFMA step: a register copy per wave costs 48 registers = a wave of occupancy)
     for (int i = tid; i < 32 * 32; i += CH_THREADS) cst[CH_W2S + (i >> 5) * CH_LDW + (i & 31)] = p.w2[i];
-    if (L3)
+    if (MODE != CH_BWD2)
         for (int i = tid; i < 64 * 32; i += CH_THREADS) cst[CH_W3S + (i >> 5) * CH_LDW + (i & 31)] = p.w3[i];
     __syncthreads();
     // per-lane statistics over the wave's blocks (lane = row of a block, register = channel): reduced over the lanes at the end
-    constexpr int NST = MODE == CH_STATS2 ? 16 : MODE == CH_STATS3 ? 32 : BWD ? 16 : 1;
+    constexpr int NST = BWD ? 16 : 1;
     float t1[NST], t2[NST], q0[MODE == CH_BWD2 ? 16 : 1], q1[MODE == CH_BWD2 ? 16 : 1], q2[MODE == CH_BWD2 ? 16 : 1];
 #pragma unroll
     for (int r = 0; r < NST; ++r) t1[r] = t2[r] = 0.f;
@@ -150,11 +132,8 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
         const float *yr = p.y + src * p.ldy + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; ++g) yo[g] = *(const f32x4 *)(yr + 8 * g);
-        if (p.dxyz) dd = *(const f32x4 *)(p.dxyz + (long long)m * 4);
-        else {
-            const float *xs = p.xyz + src * 3, *xc = p.xyz + (long long)pt * 3;
-            dd[0] = xs[0] - xc[0]; dd[1] = xs[1] - xc[1]; dd[2] = xs[2] - xc[2];
-        }
+        const float *xs = p.xyz + src * 3, *xc = p.xyz + (long long)pt * 3;
+        dd[0] = xs[0] - xc[0]; dd[1] = xs[1] - xc[1]; dd[2] = xs[2] - xc[2];
     };
     if (nb > 0) rows_of(blk0, p.idx[(long long)blk0 * 32 + j], yv, dv);
     if (nb > 1) in1 = p.idx[(long long)(blk0 + 1) * 32 + j];
@@ -198,11 +177,6 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
         for (int r = 0; r < 16; ++r) {
             acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(cst[CH_W2S + j * CH_LDW + ch_of(r, h)], x1[r], acc2, 0, 0, 0);
         }
-        if (MODE == CH_STATS2) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { t1[r % NST] += acc2[r]; t2[r % NST] += acc2[r] * acc2[r]; }
-            continue;
-        }
         float x2[16];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -226,16 +200,6 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
                     acc3[L3 ? ob : 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(cst[CH_W3S + (32 * ob + j) * CH_LDW + ch_of(r, h)], x2[r], acc3[L3 ? ob : 0], 0, 0, 0);
                 }
             }
-        }
-        if (MODE == CH_STATS3) {
-#pragma unroll
-            for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = acc3[L3 ? ob : 0][r];
-                    t1[(16 * ob + r) % NST] += v; t2[(16 * ob + r) % NST] += v * v;
-                }
-            continue;
         }
         if (MODE == CH_INFER || MODE == CH_POOL) {
             // relu(bn2), max over the S rows of a point (S consecutive lanes of a half); CH_POOL: the FIRST maximum's slot and its raw z3.
@@ -272,7 +236,7 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
             continue;
         }
         if (MODE == CH_BWD3) {
-            // ---- dz3 = a2 (du3 - s1/M - (z3 - mean) invstd s2/M), du3 = the pooled gradient at the argmax slot, 0 elsewhere ----
+            // ---- dz3 = a2 du3 (eval-mode BN), du3 = the pooled gradient at the argmax slot, 0 elsewhere ----
             f32x16 dz3[2];
 #pragma unroll
             for (int ob = 0; ob < 2; ++ob)
@@ -281,13 +245,11 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
                     const int c0 = 32 * ob + 8 * g + 4 * h;
                     const f32x4 gv = *(const f32x4 *)(p.g + pt * 64 + c0);
                     const unsigned am = *(const unsigned *)(p.argmax + pt * 64 + c0);
-                    const f32x4 sa = *(const f32x4 *)(cst + CH_KO + c0), mu = *(const f32x4 *)(cst + CH_KO + 64 + c0),
-                                u = *(const f32x4 *)(cst + CH_KO + 128 + c0), s1 = *(const f32x4 *)(cst + CH_KO + 192 + c0);
+                    const f32x4 sa = *(const f32x4 *)(cst + CH_BN2 + 128 + c0);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float d = ((int)((am >> (8 * q)) & 255u) == slot) ? gv[q] : 0.f;
-                        const float z = acc3[L3 ? ob : 0][4 * g + q];
-                        dz3[ob][4 * g + q] = p.sums ? sa[q] * (d - s1[q] - (z - mu[q]) * u[q]) : d * sa[q];
+                        dz3[ob][4 * g + q] = d * sa[q];
                     }
                 }
             // ---- dx2^T = W3^T . dz3^T: step (ob, r) contracts the output-channel pair {32 ob + c(r, 0), 32 ob + c(r, 1)} ----
@@ -333,20 +295,16 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
             continue;
         }
         if (MODE == CH_BWD2) {
-            // ---- dz2 = a1 (dU2 - s1/M - (z2 - mean) invstd s2/M) ----
+            // ---- dz2 = a1 dU2 (eval-mode BN) ----
             float dz2[16];
             const float *urow = p.dU_in + m * 32 + 4 * h;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int c0 = 8 * g + 4 * h;
                 const f32x4 dv = *(const f32x4 *)(urow + 8 * g);
-                const f32x4 sa = *(const f32x4 *)(cst + CH_KO + c0), mu = *(const f32x4 *)(cst + CH_KO + 64 + c0),
-                            u = *(const f32x4 *)(cst + CH_KO + 128 + c0), s1 = *(const f32x4 *)(cst + CH_KO + 192 + c0);
+                const f32x4 sa = *(const f32x4 *)(cst + CH_BN1 + 64 + c0);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float z = acc2[4 * g + q];
-                    dz2[4 * g + q] = p.sums ? sa[q] * (dv[q] - s1[q] - (z - mu[q]) * u[q]) : dv[q] * sa[q];
-                }
+                for (int q = 0; q < 4; ++q) dz2[4 * g + q] = dv[q] * sa[q];
             }
             // ---- dx1^T = W2^T . dz2^T ----
             f32x16 dx1;
@@ -385,8 +343,8 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
         }
     }
     // ---- statistics: the lanes of a half hold the 32 rows of every block -> sum over them (fixed tree), one row per wave ----
-    if (MODE == CH_STATS2 || MODE == CH_STATS3 || BWD) {
-        constexpr int C = MODE == CH_STATS3 ? 64 : 32;
+    if (BWD) {
+        constexpr int C = 32;
         constexpr int NROW = MODE == CH_BWD2 ? 5 : 2;
         float *prow = p.partial + wave * NROW * C;
         auto fold = [&](float v) {
@@ -396,7 +354,7 @@ __device__ __forceinline__ void setconv_chain_body(const ChainArgs &p, const int
         };
 #pragma unroll
         for (int r = 0; r < NST; ++r) {
-            const int c = (r >> 4) * 32 + ch_of(r & 15, h);
+            const int c = ch_of(r, h);
             const float a = fold(t1[r]), b = fold(t2[r]);
             if (j == 0) { prow[c] = a; prow[C + c] = b; }
             if (MODE == CH_BWD2) {
@@ -481,7 +439,6 @@ int cmf_setconv_chain_infer_batch(int n, const CmfChainInferArgs *q, void *strea
         a = ChainArgs{};
         a.M = c.M; a.N = c.N; a.S = c.S; a.lgS = c.S == 4 ? 2 : c.S == 8 ? 3 : c.S == 16 ? 4 : 5; a.idx = c.idx; a.xyz = c.xyz; a.y = c.y; a.ldy = c.ldy;
         a.wx = c.wx; a.ldwx = c.ldwx; a.bn0 = c.bn0; a.bn1 = c.bn1; a.bn2 = c.bn2; a.w2 = c.w2; a.w3 = c.w3; a.out = c.out; a.ldo = c.ldo;
-        a.inv_count = (float)(1.0 / (double)c.M);
         const long long blocks = a.M / 32;
         a.blocks_per_wave = chain_blocks_per_wave(blocks, false);
         const long long waves = (blocks + a.blocks_per_wave - 1) / a.blocks_per_wave;
@@ -508,21 +465,18 @@ long long cmf_setconv_chain_waves(long long M, int backward)
 }
 
 // mode: CH_* above.  Pointers a mode does not use may be NULL.
-int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *dxyz, const float *y, long long ldy, const float *wx,
+int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
                            long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
-                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *sums,
-                           const float *dU_in, float *dU_out, float *slabs, void *stream)
+                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *dU_in, float *dU_out,
+                           float *slabs, void *stream)
 {
     CMF_CHECK_ARG(M > 0 && M < (1ll << 31) && idx && xyz && y && wx && bn0 && bn1 && bn2 && w2 && w3 && ldy % 4 == 0 && ((uintptr_t)y & 15) == 0);
-    CMF_CHECK_ARG(!dxyz || ((uintptr_t)dxyz & 15) == 0);
     ChainArgs a{};
-    a.M = M; a.N = N; a.S = S; a.lgS = S == 4 ? 2 : S == 8 ? 3 : S == 16 ? 4 : 5; a.dxyz = dxyz; a.idx = idx; a.xyz = xyz; a.y = y; a.ldy = ldy; a.wx = wx; a.ldwx = ldwx;
+    a.M = M; a.N = N; a.S = S; a.lgS = S == 4 ? 2 : S == 8 ? 3 : S == 16 ? 4 : 5; a.idx = idx; a.xyz = xyz; a.y = y; a.ldy = ldy; a.wx = wx; a.ldwx = ldwx;
     a.bn0 = bn0; a.bn1 = bn1; a.bn2 = bn2; a.w2 = w2; a.w3 = w3; a.out = out; a.ldo = ldo; a.zsel = zsel; a.argmax = argmax;
-    a.partial = partial; a.g = g; a.sums = sums; a.inv_count = (float)(1.0 / (double)M); a.dU_in = dU_in; a.dU_out = dU_out; a.slabs = slabs;
+    a.partial = partial; a.g = g; a.dU_in = dU_in; a.dU_out = dU_out; a.slabs = slabs;
     switch (mode) {
     case CH_INFER:  CMF_CHECK_ARG(out && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0); return chain_launch<CH_INFER>(a, stream);
-    case CH_STATS2: CMF_CHECK_ARG(partial); return chain_launch<CH_STATS2>(a, stream);
-    case CH_STATS3: CMF_CHECK_ARG(partial); return chain_launch<CH_STATS3>(a, stream);
     case CH_POOL:   CMF_CHECK_ARG(out && zsel && argmax && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0); return chain_launch<CH_POOL>(a, stream);
     case CH_BWD3:   CMF_CHECK_ARG(g && argmax && dU_out && partial && slabs && (((uintptr_t)g | (uintptr_t)dU_out | (uintptr_t)argmax) & 15) == 0); return chain_launch<CH_BWD3>(a, stream);
     case CH_BWD2:   CMF_CHECK_ARG(dU_in && dU_out && partial && slabs && (((uintptr_t)dU_in | (uintptr_t)dU_out) & 15) == 0); return chain_launch<CH_BWD2>(a, stream);
@@ -534,6 +488,6 @@ int cmf_setconv_chain_infer(long long M, int N, int S, const int *idx, const flo
                             long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
                             long long ldo, void *stream)
 {
-    return cmf_setconv_chain_pass(0, M, N, S, idx, xyz, nullptr, y, ldy, wx, ldwx, bn0, bn1, bn2, w2, w3, out, ldo, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, stream);
+    return cmf_setconv_chain_pass(CH_INFER, M, N, S, idx, xyz, y, ldy, wx, ldwx, bn0, bn1, bn2, w2, w3, out, ldo, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, stream);
 }

@@ -5,5 +5,5 @@ for b in 0 1 0 1; do
 done
 for b in 0 1; do
   echo "== CMF_BODY_BATCH=$b: first encoder alone (both clouds, forward + backward, isolated kernel durations)"
-  CMF_BODY_BATCH=$b ENC1_SERIAL=1 CMF_CHAIN_TRAIN=0 python tools/enc1_profile.py 2>&1 | grep -v "Warning\|_warn_once\|amdgpu.ids" | head -16 | cut -c1-150
+  CMF_BODY_BATCH=$b ENC1_SERIAL=1 python tools/enc1_profile.py 2>&1 | grep -v "Warning\|_warn_once\|amdgpu.ids" | head -16 | cut -c1-150
 done

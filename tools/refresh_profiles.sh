@@ -22,7 +22,7 @@ python tools/trace_overlap.py $(find /tmp/p1 -name "*kernel_trace.csv" | head -1
 cp $(find /tmp/p2 -name "*kernel_stats.csv" | head -1) $R/fwd_kernel_stats.csv
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p3 -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-rooflines --no-config2 --serial > /dev/null 2>&1)
 cp $(find /tmp/p3 -name "*kernel_stats.csv" | head -1) $R/train_serial_kernel_stats.csv
-for c in 0 1; do echo "== CMF_CHAIN_TRAIN=$c (ENC1_SERIAL=1: isolated kernel durations)"; ENC1_SERIAL=1 CMF_CHAIN_TRAIN=$c python tools/enc1_profile.py 2>&1 | grep -v "Warning\|_warn_once\|amdgpu.ids" | head -22; done > $R/enc1_profile.txt
+(echo "== ENC1_SERIAL=1: isolated kernel durations"; ENC1_SERIAL=1 python tools/enc1_profile.py 2>&1 | grep -v "Warning\|_warn_once\|amdgpu.ids" | head -22) > $R/enc1_profile.txt
 python tools/gemm_vendor_compare.py 2>&1 | grep -v amdgpu.ids > $R/gemm_vendor_compare.txt
 python tools/host_time_probe.py 20 2>&1 | grep -v amdgpu.ids > $R/host_time_probe.txt
 python tools/phase_probe.py 2>&1 | grep -v amdgpu.ids > $R/phase_probe.txt

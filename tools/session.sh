@@ -102,10 +102,6 @@ pm_hbm() {             # HBM-bound kernels of the product path: durations + FETC
     python tools/pm_table.py $(find /tmp/q1 -name "*kernel_trace.csv" | head -1) $(find /tmp/q2 -name "*counter_collection.csv" | head -1) \
         $(find /tmp/q3 -name "*counter_collection.csv" | head -1) $R/pm_probe.out > $R/pm_hbm_kernels.md; cat $R/pm_hbm_kernels.md
 }
-bnb_ab() {             # BN backward of the 512 -> 256 layer inside the weight-gradient GEMM (default) against the stand-alone pass
-    python -m pytest tests/test_gpu_gemm.py -x -q -m gpu -k "fused_bn_backward or block or setconv or set_conv" 2>&1 | grep -E "passed|failed|Error|assert" | tail -8
-    for v in 0 1 0 1; do CMF_BNB_FUSED=$v python bench.py --full --steps 40 --no-cpu-baseline --no-op-rooflines 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('fused $v', d['ms_per_step'], d['roofline']['frac'], d['roofline_isolated']['frac'])"; done | tee $R/bnb_ab.txt
-}
 ar_trace() {            # kernel + HIP API trace of the step's tail with and without the forced world-1 all-reduce (tools/step_tail_probe.py)
     for v in base forced; do
         rm -rf /tmp/ar_$v
