@@ -20,6 +20,13 @@ SIGNATURES = {
     "cmf_ball_query": [_ci, _ci, _ci, _cf, _ci, _vp, _vp, _vp, _vp],
     "cmf_ball_query_multi": [_ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _vp],
     "cmf_setconv_queries": [_ci, _vp, _vp],
+    # ragged batches (per-sample counts in device memory)
+    "cmf_ball_query_multi_counted": [_ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_setconv_queries_counted": [_ci, _vp, _vp, _vp],
+    "cmf_knn_counted": [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_global_max_cat_counted": [_ci, _ci, _ci, _vp, _ll, _vp, _ll, _vp, _vp, _vp],
+    "cmf_ego_refine_counted": [_ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_eval_metrics_counted": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
     "cmf_group_points": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp],
     "cmf_group_points_grad": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp],
     "cmf_query_and_group": [_ci, _ci, _ci, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp],

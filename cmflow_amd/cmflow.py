@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from . import fused_blocks as FB
-from .radarflow_util import (FeatureCorrelator, FlowHead, MotionHead, MultiScaleEncoder, ego_refine, weighted_kabsch)
+from .radarflow_util import (FeatureCorrelator, FlowHead, MotionHead, MultiScaleEncoder, ego_refine, ego_refine_counted,
+                             weighted_kabsch)
 
 
 class CMFlow(nn.Module):
@@ -131,7 +132,8 @@ class CMFlow(nn.Module):
         """cmflow.py:128-169"""
         return weighted_kabsch(A, B, W)
 
-    def _heads(self, final_features, pc1, label_m, mode):
+    def _head_outputs(self, final_features):
+        """The flow and the motion head (cmflow.py:171-176) on final_features (B,C,N) -> output (B,3,N), stat_cls (B,1,N)."""
         if self.head_streams and final_features.is_cuda:
             # the two heads are independent chains of small GEMMs (N = 256: a third of the CUs each): the motion head
             # runs on a side stream next to the flow head; autograd replays each backward on its forward stream
@@ -152,6 +154,10 @@ class CMFlow(nn.Module):
             ff = final_features.transpose(1, 2)                       # (B,N,512) view
             output = self.fp.forward_pm(ff).transpose(1, 2)
             stat_cls = self.mp.forward_pm(ff).transpose(1, 2)
+        return output, stat_cls
+
+    def _heads(self, final_features, pc1, label_m, mode):
+        output, stat_cls = self._head_outputs(final_features)
         if (mode == 'train') and (label_m is not None):
             scores = label_m.unsqueeze(1)
         else:
@@ -168,6 +174,87 @@ class CMFlow(nn.Module):
     def forward(self, pc1, pc2, feature1, feature2, label_m, mode):
         final_features = self.Backbone(pc1, pc2, feature1, feature2)
         return self._heads(final_features, pc1, label_m, mode)
+
+
+    # ---- ragged batches: B frame pairs of their own point counts in one call (inference) -----------------------------------------
+    # The reference tests on the whole cloud of every frame, one pair per forward (main.py:203 batch_size = 1; dataset/vod.py:92-111
+    # resamples for training only), N1 != N2.  forward_ragged runs B such pairs as one padded batch: a sample's size enters the
+    # arithmetic in five places -- the ball queries of both encoders, the two kNN searches of the cost volume, the global max-pools,
+    # the Kabsch weights / sums and (eval_util) the metrics -- and each has a counted kernel; everything else is row-wise in eval mode
+    # and runs on the padded rows, which stay finite and are never read by a valid row.
+    RAGGED_MAX_POINTS = 1024                       # the counted one-scan ball query (cmflow_hip.h)
+
+    def _check_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate):
+        if self.training:
+            raise RuntimeError("forward_ragged is inference only: call net.eval() first (train-mode BatchNorm statistics over padded "
+                               "rows are a different computation)")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_ragged is inference only: call it under torch.no_grad()")
+        B, _, N1 = pc1.shape
+        N2 = pc2.shape[2]
+        if pc2.shape[0] != B or feature1.shape[0] != B or feature2.shape[0] != B or feature1.shape[2] != N1 or feature2.shape[2] != N2:
+            raise ValueError("forward_ragged: pc1 / feature1 are (B,3,Nmax1), pc2 / feature2 (B,3,Nmax2)")
+        for n in (npoints1, npoints2):
+            if n.dtype != torch.int32 or n.shape != (B,) or n.device != pc1.device:
+                raise ValueError("forward_ragged: npoints1 / npoints2 are (B,) int32 tensors on the inputs' device")
+        if max(N1, N2) > self.RAGGED_MAX_POINTS:
+            raise ValueError("forward_ragged covers clouds of up to %d points; got Nmax1 = %d, Nmax2 = %d" % (self.RAGGED_MAX_POINTS, N1, N2))
+        if validate:                                                # a device -> host sync
+            lo1, hi1, lo2, hi2 = (int(v) for v in torch.stack((npoints1.min(), npoints1.max(), npoints2.min(), npoints2.max())).tolist())
+            k = self.fc_layer.nsample
+            if lo1 < 1 or hi1 > N1:
+                raise ValueError("forward_ragged: npoints1 must lie in [1, %d]; got [%d, %d]" % (N1, lo1, hi1))
+            if lo2 < k or hi2 > N2:
+                raise ValueError("forward_ragged: npoints2 must lie in [%d, %d] (the cost volume takes %d neighbours in cloud 2; the "
+                                 "reference's torch.topk raises below that); got [%d, %d]" % (k, N2, k, lo2, hi2))
+
+    def _propagate_ragged(self, pc1, pc2, feature1, feature2, n1, n2):
+        """_propagate_pm on padded clouds with per-sample counts; returns prop (B,Nm,256) POINT-major with Nm = max(Nmax1, Nmax2)."""
+        B, _, N1 = pc1.shape
+        N2 = pc2.shape[2]
+        Nm = max(N1, N2)
+        pad = lambda t, n: t if n == Nm else torch.nn.functional.pad(t, (0, Nm - n))      # zero rows: finite, never read by a valid row
+        x1, x2, a1p, a2p = FB.inputs_point_major(pad(pc1, N1), pad(pc2, N2), pad(feature1, N1), pad(feature2, N2))
+        a1 = a1p[:, :, :feature1.shape[1]]
+        # both clouds padded to one size share ONE call of the (weight-shared) first encoder, as in the dense eval path
+        f12 = self.mse_layer.forward_pm_ragged(torch.cat((x1, x2), dim=0), torch.cat((a1p, a2p), dim=0), torch.cat((n1, n2)))
+        f1, f2 = FB.global_max_cat_counted(f12[:B], n1), FB.global_max_cat_counted(f12[B:], n2)     # (B,Nm,512)
+        cor = self.fc_layer.forward_pm(x1, x2, f1, f2, n1, n2)                                 # (B,Nm,512)
+        n_grad, n_tail = f1.shape[2] + cor.shape[2], a1.shape[2]
+        emb = torch.cat((f1, cor, a1, a1.new_zeros(B, Nm, -(n_grad + n_tail) % 16)), dim=2)
+        prop = self._second_encoder().forward_pm_ragged(x1, emb, n1, n_tail=n_tail)            # (B,Nm,256)
+        self.last = {"pc1_features": f1[:, :N1, :256].transpose(1, 2), "pc2_features": f2[:, :N2, :256].transpose(1, 2),
+                     "cor_features": cor[:, :N1].transpose(1, 2), "prop_features": prop[:, :N1].transpose(1, 2)}
+        return prop
+
+    def _final_features_ragged(self, prop, n1, gfeat_prev):
+        """cmflow.py:89-91: cat(prop, max over the sample's valid points) as (B,512,Nm)."""
+        return FB.global_max_cat_counted(prop, n1).transpose(1, 2), None
+
+    def _forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat_prev):
+        self._check_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate)
+        N1 = pc1.shape[2]
+        prop = self._propagate_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2)
+        Nm = prop.shape[1]
+        final_features, gfeat = self._final_features_ragged(prop, npoints1, gfeat_prev)
+        output, stat_cls = self._head_outputs(final_features)
+        pc1m = pc1 if N1 == Nm else torch.nn.functional.pad(pc1, (0, Nm - N1))
+        pre_trans, sf_agg, mask, stat = ego_refine_counted(output, pc1m, stat_cls.squeeze(1), npoints1, self.score_eps or 0.0, self.stat_thres)
+        if N1 != Nm:
+            sf_agg, stat, mask = sf_agg[:, :, :N1].contiguous(), stat[:, :N1].contiguous(), mask[:, :N1].contiguous()
+        return sf_agg, stat.unsqueeze(1), pre_trans, mask, gfeat
+
+    def forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate=False):
+        """B frame pairs with their own point counts in one call -- the reference's test protocol (main.py:203, batch_size = 1 on whole
+        frames) batched.  pc1, feature1 (B,3,Nmax1), pc2, feature2 (B,3,Nmax2) padded; npoints1, npoints2 (B,) int32 on the device,
+        1 <= npoints1[i] <= Nmax1, 8 <= npoints2[i] <= Nmax2 (8: the cost volume's neighbours in cloud 2).  Nmax <= 1024.
+        -> (sf_agg (B,3,Nmax1), stat_cls (B,1,Nmax1), pre_trans (B,4,4), mask (B,Nmax1) bool): for sample i the slices [..., :npoints1[i]]
+        are what forward(pc1[i:i+1, :, :n1], pc2[i:i+1, :, :n2], ..., None, 'test') returns; padded slots: flow 0, stat_cls 0, mask False.
+        Inference only: eval() and torch.no_grad(), else RuntimeError.  The content of the padded input slots does not influence any
+        valid output as long as it is finite; NaN / Inf there is the caller's error and is not caught.  validate=True checks the counts
+        on the host (ValueError) -- a device -> host synchronisation; without it the counts are trusted (the kernels clamp them to the
+        padded size, so a wrong count gives wrong numbers, not a wild access)."""
+        return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, None)[:4]
 
 
 class CMFlow_T(CMFlow):
@@ -194,6 +281,21 @@ class CMFlow_T(CMFlow):
     def forward(self, pc1, pc2, feature1, feature2, label_m, mode, gfeat):
         final_features, gfeat = self.Backbone(pc1, pc2, feature1, feature2, gfeat)
         return (*self._heads(final_features, pc1, label_m, mode), gfeat)
+
+    def _final_features_ragged(self, prop, n1, gfeat_prev):
+        """cmflow_t.py Backbone on ragged samples: the GRU input is the max over each sample's VALID points (the counted global max;
+        its second half is that maximum on every row)."""
+        B, Nm, C = prop.shape
+        gfeat = FB.global_max_cat_counted(prop, n1)[:, 0, C:]
+        if gfeat_prev is None:
+            gfeat_prev = torch.zeros_like(gfeat)
+        gfeat_new = self.gru(gfeat.unsqueeze(0), gfeat_prev.unsqueeze(0))[0].squeeze(0)
+        return torch.cat((prop.transpose(1, 2), gfeat_new.unsqueeze(2).expand(-1, -1, Nm)), dim=1), gfeat_new
+
+    def forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, gfeat, validate=False):
+        """CMFlow.forward_ragged with the recurrent global feature carried across the frames of a clip (clip_util.py:34-62):
+        gfeat (B,256) of the previous frame or None -> (sf_agg, stat_cls, pre_trans, mask, gfeat)."""
+        return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat)
 
 
 def init_model(args, device="cuda"):

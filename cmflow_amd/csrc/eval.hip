@@ -36,29 +36,34 @@ __device__ __forceinline__ double ev_resolution(float r, float st, float ct, flo
     return (x + y) + z;
 }
 
+// COUNTED (cmf_eval_metrics_counted, ragged samples): the sample's rows are ld apart in memory and its sums run over its first
+// cnt[bs] rows (one workgroup per sample: a scalar) -- the same terms in the same order as the dense form on the truncated sample.
+// Dense: cnt is not read and ld == n.
+template <bool COUNTED>
 __global__ __launch_bounds__(EV_THREADS) void eval_sample_kernel(
-    int n, const float *__restrict__ pc, const float *__restrict__ pred, const float *__restrict__ labels,
+    int ld, const int *__restrict__ cnt, const float *__restrict__ pc, const float *__restrict__ pred, const float *__restrict__ labels,
     const float *__restrict__ mask, const float *__restrict__ pred_m, const float *__restrict__ gt_trans,
     const float *__restrict__ pred_trans, double r_res, double th_res, double ph_res, double *__restrict__ partial)
 {
     __shared__ double red[EV_THREADS / 64];
     const int bs = blockIdx.x, tid = threadIdx.x;
-    const float *p = pc + (size_t)bs * 3 * n;
+    const int n = COUNTED ? max(0, min(cnt[bs], ld)) : ld;
+    const float *p = pc + (size_t)bs * 3 * ld;
     double acc[14];
 #pragma unroll
     for (int t = 0; t < 14; ++t) acc[t] = 0.0;
     const bool do_sf = pc != nullptr, do_seg = pred_m != nullptr;
     for (int i = tid; i < n; i += EV_THREADS) {
-        const float m = mask ? mask[(size_t)bs * n + i] : 0.f;
+        const float m = mask ? mask[(size_t)bs * ld + i] : 0.f;
         if (do_seg) {
-            const float pm = pred_m[(size_t)bs * n + i];
+            const float pm = pred_m[(size_t)bs * ld + i];
             acc[10] += (pm == 1.f && m == 1.f) ? 1.0 : 0.0;
             acc[11] += (pm == 0.f && m == 0.f) ? 1.0 : 0.0;
             acc[12] += (pm == 1.f && m == 0.f) ? 1.0 : 0.0;
             acc[13] += (pm == 0.f && m == 1.f) ? 1.0 : 0.0;
         }
         if (!do_sf) continue;
-        const size_t o = ((size_t)bs * n + i) * 3;
+        const size_t o = ((size_t)bs * ld + i) * 3;
         const float dx = pred[o] - labels[o], dy = pred[o + 1] - labels[o + 1], dz = pred[o + 2] - labels[o + 2];
         const float err = sqrtf(((dx * dx + dy * dy) + dz * dz) + 1e-20f);
         const float lx = labels[o], ly = labels[o + 1], lz = labels[o + 2];
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_sample_kernel(
         acc[1] += (err <= 0.05f || rel <= 0.05f) ? 1.0 : 0.0;
         acc[2] += (err <= 0.10f || rel <= 0.10f) ? 1.0 : 0.0;
         // resolution-normalised error: radar vs lidar cartesian resolution at this point
-        const float x = p[i], y = p[n + i], z = p[2 * n + i];
+        const float x = p[i], y = p[ld + i], z = p[2 * ld + i];
         const float r = sqrtf((x * x + y * y) + z * z);
         const float th = asinf(z / r), ph = atan2f(y, x);
         const float st = sinf(th), ct = cosf(th), sp = sinf(ph), cp = cosf(ph);
@@ -133,6 +138,41 @@ __global__ __launch_bounds__(64) void eval_finalize_kernel(int b, int n, const d
         metrics[11] = tp / ((tp + fn) + 1e-10);
         metrics[12] = s[14] / (double)b; metrics[13] = s[15] / (double)b;
     }
+}
+
+// Ragged samples: the metrics of every sample on its own -- eval_finalize_kernel's formulae with b = 1, n = cnt[i] -- then their mean
+// over the samples in index order: what main_util.py:176-192 accumulates with the test loader's batch size 1 (main.py:203).
+__global__ __launch_bounds__(64) void eval_finalize_counted_kernel(int b, int ld, const int *__restrict__ cnt, const double *__restrict__ partial,
+                                                                   double *__restrict__ metrics)
+{
+    const int t = threadIdx.x;
+    if (t >= 14) return;
+    double acc = 0.0;
+    for (int i = 0; i < b; ++i) {
+        const double *s = partial + (size_t)i * EV_PART;
+        const double n = (double)max(0, min(cnt[i], ld));
+        const double mov = s[4] / (s[5] + 1e-6), stat = s[6] / s[7];          // np.mean of an empty selection is NaN
+        const double tp = s[10], tn = s[11], fp = s[12], fn = s[13];
+        double v;
+        switch (t) {
+        case 0: v = s[3] / n; break;
+        case 1: v = (mov + stat) / 2.0; break;
+        case 2: v = mov; break;
+        case 3: v = stat; break;
+        case 4: v = s[8] / n; break;
+        case 5: v = s[9] / n; break;
+        case 6: v = s[0] / n; break;
+        case 7: v = s[1] / n; break;
+        case 8: v = s[2] / n; break;
+        case 9: v = (tp + tn) / (((tp + tn) + fp) + fn); break;
+        case 10: v = 0.5 * (tp / (((tp + fp) + fn) + 1e-10) + tn / (((tn + fp) + fn) + 1e-10)); break;
+        case 11: v = tp / ((tp + fn) + 1e-10); break;
+        case 12: v = s[14]; break;
+        default: v = s[15]; break;
+        }
+        acc += v;
+    }
+    metrics[t] = acc / (double)b;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -213,8 +253,21 @@ extern "C" int cmf_eval_metrics(int b, int n, const float *pc, const float *pred
     // mask), pose (gt_trans, pred_trans); the metrics of a skipped group are not meaningful
     CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_sample_kernel, dim3(b), dim3(EV_THREADS), 0, st, n, pc, pred, labels, mask, pred_m, gt_trans,
+    hipLaunchKernelGGL(eval_sample_kernel<false>, dim3(b), dim3(EV_THREADS), 0, st, n, (const int *)nullptr, pc, pred, labels, mask, pred_m, gt_trans,
                        pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
     hipLaunchKernelGGL(eval_finalize_kernel, dim3(1), dim3(64), 0, st, b, n, workspace, metrics);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_eval_metrics_counted(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
+                                        const float *pred_m, const float *gt_trans, const float *pred_trans,
+                                        float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream)
+{
+    CMF_CHECK_ARG(b > 0 && n > 0 && cnt && metrics && workspace);
+    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(eval_sample_kernel<true>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
+                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    hipLaunchKernelGGL(eval_finalize_counted_kernel, dim3(1), dim3(64), 0, st, b, n, cnt, workspace, metrics);
     return cmf_launch_status();
 }

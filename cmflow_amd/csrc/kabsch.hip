@@ -98,14 +98,16 @@ __device__ __forceinline__ double det3(const double *M)
 }
 
 // one sample (one wavefront): a, b (3,n), w (n) -> T (4,4) [lane 0 writes], x = the sample's aux record or null
-__device__ __forceinline__ void kabsch_fwd_sample(int n, const float *a, const float *b, const float *w, float *T, double *x, int lane)
+// (ld: stride between the three coordinate planes; -1 = n, the dense layout)
+__device__ __forceinline__ void kabsch_fwd_sample(int n, const float *a, const float *b, const float *w, float *T, double *x, int lane, int ld = -1)
 {
+    if (ld < 0) ld = n;
     // pass 1: weighted centroids  (cmflow.py:138-139)
     double sw = 0, ca[3] = {0, 0, 0}, cb[3] = {0, 0, 0};
     for (int i = lane; i < n; i += CMF_WAVE) {
         const double wi = w[i];
         sw += wi;
-        for (int k = 0; k < 3; ++k) { ca[k] += wi * a[k * n + i]; cb[k] += wi * b[k * n + i]; }
+        for (int k = 0; k < 3; ++k) { ca[k] += wi * a[k * ld + i]; cb[k] += wi * b[k * ld + i]; }
     }
     sw = wave_sum(sw);
     for (int k = 0; k < 3; ++k) { ca[k] = wave_sum(ca[k]); cb[k] = wave_sum(cb[k]); }
@@ -114,7 +116,7 @@ __device__ __forceinline__ void kabsch_fwd_sample(int n, const float *a, const f
     for (int i = lane; i < n; i += CMF_WAVE) {
         const double wi = w[i];
         double da[3], db[3];
-        for (int k = 0; k < 3; ++k) { da[k] = a[k * n + i] - ca[k]; db[k] = (b[k * n + i] - cb[k]) * wi; }
+        for (int k = 0; k < 3; ++k) { da[k] = a[k * ld + i] - ca[k]; db[k] = (b[k * ld + i] - cb[k]) * wi; }
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) H[r * 3 + c] += da[r] * db[c];
     }
@@ -155,35 +157,52 @@ __global__ __launch_bounds__(CMF_WAVE) void kabsch_fwd_kernel(
 //   sf = mask ? (R pc1 + t - pc1) : flow
 // One wavefront per sample as above.  w and B are written out (the backward pass reads them; a lane re-reads only what it wrote
 // itself).  As torch ops this was ~10 small kernels forward and ~15 backward on the main stream with nothing beside them.
+// COUNTED (cmf_ego_refine_counted, ragged samples): sample bs has n = cnt[bs] <= ld points, its rows ld apart in memory (one wavefront
+// per sample: the count is a scalar).  Everything summed over the points -- the score sum, the weighted centroids, the covariance -- runs
+// over the n rows in the same lane-strided order, so the transform and the valid slices equal the dense call's on the truncated sample
+// bit for bit; the slots behind n are written as zeros.  stat (b,ld), optional: the scores with the padded slots zeroed (the model's
+// stat_cls output).  Dense: n == ld, cnt and stat are not read.
+template <bool COUNTED>
 __global__ __launch_bounds__(CMF_WAVE) void ego_refine_fwd_kernel(
-    int n, float eps, float thres, const float *__restrict__ pc1, const float *__restrict__ flow, const float *__restrict__ score,
-    float *W, float *Bm, float *__restrict__ trans, double *__restrict__ aux, float *__restrict__ sf, unsigned char *__restrict__ mask)
+    int ld, float eps, float thres, const float *__restrict__ pc1, const float *__restrict__ flow, const float *__restrict__ score,
+    float *W, float *Bm, float *__restrict__ trans, double *__restrict__ aux, float *__restrict__ sf, unsigned char *__restrict__ mask,
+    const int *__restrict__ cnt, float *__restrict__ stat)
 {
     const int bs = blockIdx.x, lane = threadIdx.x;
-    const float *a = pc1 + (size_t)bs * 3 * n, *f = flow + (size_t)bs * 3 * n, *sc = score + (size_t)bs * n;
-    float *w = W + (size_t)bs * n, *b = Bm + (size_t)bs * 3 * n;
+    const int n = COUNTED ? max(0, min(cnt[bs], ld)) : ld;
+    const float *a = pc1 + (size_t)bs * 3 * ld, *f = flow + (size_t)bs * 3 * ld, *sc = score + (size_t)bs * ld;
+    float *w = W + (size_t)bs * ld, *b = Bm + (size_t)bs * 3 * ld;
     double ssum = 0.0;
     for (int i = lane; i < n; i += CMF_WAVE) ssum += (double)(sc[i] + eps);
     const float tot = (float)wave_sum(ssum);
     for (int i = lane; i < n; i += CMF_WAVE) {
         w[i] = (sc[i] + eps) / tot;
-        for (int k = 0; k < 3; ++k) b[k * n + i] = a[k * n + i] + f[k * n + i];
+        for (int k = 0; k < 3; ++k) b[k * ld + i] = a[k * ld + i] + f[k * ld + i];
     }
     __shared__ float Tsh[16];                       // lane 0 solves; the wave reads the transform back from LDS
-    kabsch_fwd_sample(n, a, b, w, Tsh, aux ? aux + (size_t)bs * KB_AUX : nullptr, lane);
+    if (COUNTED) kabsch_fwd_sample(n, a, b, w, Tsh, aux ? aux + (size_t)bs * KB_AUX : nullptr, lane, ld);
+    else kabsch_fwd_sample(n, a, b, w, Tsh, aux ? aux + (size_t)bs * KB_AUX : nullptr, lane);
     __syncthreads();
     if (lane < 16) trans[(size_t)bs * 16 + lane] = Tsh[lane];
     float Tm[12];
     for (int k = 0; k < 12; ++k) Tm[k] = Tsh[k];
     for (int i = lane; i < n; i += CMF_WAVE) {
-        const float x = a[i], y = a[n + i], z = a[2 * n + i];
+        const float x = a[i], y = a[ld + i], z = a[2 * ld + i];
         const bool m = sc[i] > thres;
-        mask[(size_t)bs * n + i] = m ? 1 : 0;
+        mask[(size_t)bs * ld + i] = m ? 1 : 0;
+        if (COUNTED && stat) stat[(size_t)bs * ld + i] = sc[i];
         for (int r = 0; r < 3; ++r) {
-            const float rig = fmaf(Tm[r * 4 + 2], z, fmaf(Tm[r * 4 + 1], y, Tm[r * 4 + 0] * x)) + Tm[r * 4 + 3] - a[r * n + i];
-            sf[(size_t)bs * 3 * n + r * n + i] = m ? rig : f[r * n + i];
+            const float rig = fmaf(Tm[r * 4 + 2], z, fmaf(Tm[r * 4 + 1], y, Tm[r * 4 + 0] * x)) + Tm[r * 4 + 3] - a[r * ld + i];
+            sf[(size_t)bs * 3 * ld + r * ld + i] = m ? rig : f[r * ld + i];
         }
     }
+    if (COUNTED)
+        for (int i = n + lane; i < ld; i += CMF_WAVE) {            // padding of a ragged sample: defined outputs
+            mask[(size_t)bs * ld + i] = 0;
+            if (stat) stat[(size_t)bs * ld + i] = 0.f;
+            w[i] = 0.f;
+            for (int r = 0; r < 3; ++r) { sf[(size_t)bs * 3 * ld + r * ld + i] = 0.f; b[r * ld + i] = 0.f; }
+        }
 }
 
 // Backward.  With M = H^T = Z P (Z = V U^T orthogonal, P = U S U^T), the derivative of the
@@ -343,8 +362,20 @@ extern "C" int cmf_ego_refine(int b, int n, float eps, float thres, const float 
     CMF_CHECK_ARG(b >= 0 && n > 0);
     if (b == 0) return 0;
     CMF_CHECK_ARG(pc1 && flow && score && W && Bm && trans && sf && mask);
-    hipLaunchKernelGGL(ego_refine_fwd_kernel, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm, trans,
-                       aux, sf, mask);
+    hipLaunchKernelGGL(ego_refine_fwd_kernel<false>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm, trans,
+                       aux, sf, mask, (const int *)nullptr, (float *)nullptr);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_ego_refine_counted(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score,
+                                      const int *cnt, float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask,
+                                      float *stat, void *stream)
+{
+    CMF_CHECK_ARG(b >= 0 && n > 0);
+    if (b == 0) return 0;
+    CMF_CHECK_ARG(pc1 && flow && score && cnt && W && Bm && trans && sf && mask);
+    hipLaunchKernelGGL(ego_refine_fwd_kernel<true>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm, trans,
+                       aux, sf, mask, cnt, stat);
     return cmf_launch_status();
 }
 

@@ -1279,9 +1279,16 @@ extern "C" int cmf_bn_bwd_apply(long long M, int C, float *dU, const float *z, l
 constexpr int GM_THREADS = 256;
 constexpr int GM_CH = 64;
 
+// COUNTED (cmf_global_max_cat_counted, ragged samples): the maximum and arg of sample b run over its rows < cnt[b] (one sample per
+// workgroup row: a scalar) -- the same per-thread row walk and the same fold across the row groups, so values and arg equal the dense
+// call's on the truncated sample bit for bit; the rows behind the count are padding: copied and given the sample's maximum like any
+// row, never part of it.  Dense: cnt is not read.
+template <bool COUNTED>
 __global__ __launch_bounds__(GM_THREADS) void global_max_cat_kernel(
-    int N, int C, const float *__restrict__ f, long long ldf, float *__restrict__ out, long long ldo, int *__restrict__ arg)
+    int N, int C, const float *__restrict__ f, long long ldf, float *__restrict__ out, long long ldo, int *__restrict__ arg,
+    const int *__restrict__ cnt)
 {
+    const int Nv = COUNTED ? max(0, min(cnt[blockIdx.y], N)) : N;
     __shared__ float smax[GM_THREADS / 16][GM_CH];
     __shared__ int sarg[GM_THREADS / 16][GM_CH];
     const int b = blockIdx.y, c0 = blockIdx.x * GM_CH;
@@ -1292,8 +1299,8 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_kernel(
     float *ob = out + (long long)b * N * ldo;
     float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int am[4] = {0, 0, 0, 0};
-    if (live)
-        for (int n = rg; n < N; n += GM_THREADS / 16) {
+    if (live) {
+        for (int n = rg; n < Nv; n += GM_THREADS / 16) {
             const float4 v = *(const float4 *)(fb + (long long)n * ldf + c);
             *(float4 *)(ob + (long long)n * ldo + c) = v;
             const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -1301,6 +1308,10 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_kernel(
             for (int i = 0; i < 4; ++i)
                 if (vv[i] > m[i]) { m[i] = vv[i]; am[i] = n; }
         }
+        if (COUNTED)
+            for (int n = Nv + rg; n < N; n += GM_THREADS / 16)      // padded rows: copied only
+                *(float4 *)(ob + (long long)n * ldo + c) = *(const float4 *)(fb + (long long)n * ldf + c);
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) { smax[rg][tc + i] = m[i]; sarg[rg][tc + i] = am[i]; }
     __syncthreads();
@@ -1366,7 +1377,19 @@ extern "C" int cmf_global_max_cat(int B, int N, int C, const float *f, long long
     CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldo >= 2 * C && ldf % 4 == 0 && ldo % 4 == 0 && B < 65536);
     if (B == 0) return 0;
     CMF_CHECK_ARG(f && out && arg && (((uintptr_t)f | (uintptr_t)out | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_kernel, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out, ldo, arg);
+    hipLaunchKernelGGL(global_max_cat_kernel<false>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out, ldo, arg,
+                       (const int *)nullptr);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_global_max_cat_counted(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg,
+                                          const int *cnt, void *stream)
+{
+    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldo >= 2 * C && ldf % 4 == 0 && ldo % 4 == 0 && B < 65536);
+    if (B == 0) return 0;
+    CMF_CHECK_ARG(f && out && arg && cnt && (((uintptr_t)f | (uintptr_t)out | (uintptr_t)arg) & 15) == 0);
+    hipLaunchKernelGGL(global_max_cat_kernel<true>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out,
+                       ldo, arg, cnt);
     return cmf_launch_status();
 }
 

@@ -481,7 +481,8 @@ static int setconv_forward_part(const cmf_setconv_desc *d, void *st, int part)
 
 extern "C" int cmf_setconv_forward(const cmf_setconv_desc *d, void *st) { return setconv_forward_part(d, st, 0); }
 
-extern "C" int cmf_setconv_queries(int n, const cmf_setconv_desc *descs, void *stream)
+// counts: NULL (dense), or per block the device array (B) int32 of its samples' point counts (ragged samples: cmf_setconv_queries_counted)
+static int setconv_queries(int n, const cmf_setconv_desc *descs, const int *const *counts, void *stream)
 {
     CMF_CHECK_ARG(n >= 0 && (n == 0 || descs));
     int i = 0;
@@ -502,6 +503,10 @@ extern "C" int cmf_setconv_queries(int n, const cmf_setconv_desc *descs, void *s
         }
         int ns_chk[4];
         for (int q = 0; q < nq; ++q) ns_chk[q] = descs[i + q].S;
+        if (counts) {                                         // ragged samples: the nested one-scan query only (n <= 1024), never an uncounted path
+            CMF_CHECK_ARG(cmf_ball_query_multi_takes(d0.N, nq, ns_chk));
+            for (int q = 0; q < nq * nclouds; ++q) CMF_CHECK_ARG(counts[i + q] && counts[i + q] == counts[i + (q / nq) * nq]);
+        }
         if (!cmf_ball_query_multi_takes(d0.N, nq, ns_chk)) {  // large clouds (cell grid) / lists too long for one launch: the single-scale queries
             for (int q = 0; q < nq * nclouds; ++q) {
                 const cmf_setconv_desc &d = descs[i + q];
@@ -522,11 +527,23 @@ extern "C" int cmf_setconv_queries(int n, const cmf_setconv_desc *descs, void *s
                     if (c == 0) { radii[q] = d.radius; ns[q] = d.S; }
                 }
             }
-            CMF_TRY(cmf_ball_query_multi(d0.B, d0.N, d0.N, nq, radii, ns, nclouds, ctr, cloud, idx, 1, stream));
+            if (counts) {
+                const int *cnt[2] = {counts[i], counts[i + (nclouds - 1) * nq]};
+                CMF_TRY(cmf_ball_query_multi_counted(d0.B, d0.N, d0.N, nq, radii, ns, nclouds, ctr, cloud, idx, cnt, cnt, stream));
+            } else
+                CMF_TRY(cmf_ball_query_multi(d0.B, d0.N, d0.N, nq, radii, ns, nclouds, ctr, cloud, idx, 1, stream));
         }
         i += nq * nclouds;
     }
     return 0;
+}
+
+extern "C" int cmf_setconv_queries(int n, const cmf_setconv_desc *descs, void *stream) { return setconv_queries(n, descs, nullptr, stream); }
+
+extern "C" int cmf_setconv_queries_counted(int n, const cmf_setconv_desc *descs, const int *const *counts, void *stream)
+{
+    CMF_CHECK_ARG(n == 0 || counts);
+    return setconv_queries(n, descs, counts, stream);
 }
 
 // ---- the per-point tails of n blocks in batched launches (cmf_common.h "batched launches") ---------------------------

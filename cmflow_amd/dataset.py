@@ -1,7 +1,8 @@
 """Sample I/O: the View-of-Delft scene-flow sample format and its Datasets -- mirror of ``dataset/vod.py``
 (vodDataset :14-137; format described in src/GETTING_STARTED.md:97-106), of ``dataset/vod_clip.py`` (vodClipDataset
 :14-198, the mini-clip loader CMFlow-T trains on) and of ``extract_data_info`` / ``extract_data_info_clip``
-(main_util.py:21-36, clip_util.py:81-96).
+(main_util.py:21-36, clip_util.py:81-96); ``collate_ragged`` / ``extract_data_info_ragged`` batch the evaluation-mode items (whole
+frames of their own sizes) for ``CMFlow.forward_ragged``.
 
 One sample = one JSON file ``<root>/<partition>/<clip>/<k>_*.json`` with
     pc1, pc2          [n][5]  x, y, z, RCS, v_r          (features fed to the net: [v_r, RCS, RCS], vod.py:62-63)
@@ -174,6 +175,42 @@ def extract_data_info(data, device="cuda"):
 def extract_data_info_clip(seq_data, idx, device="cuda"):
     """clip_util.py:81-96: frame ``idx`` of a collated mini-clip batch -> the tuple of extract_data_info."""
     return extract_data_info(tuple(t[:, idx] for t in seq_data), device=device)
+
+
+def collate_ragged(items):
+    """``collate_fn`` for the evaluation-mode items of vodDataset / vodClipDataset (the reference's 11-tuples, whole frames of their
+    own sizes: dataset/vod.py:92-111 resamples for training only, main.py:203 therefore tests with batch_size = 1): B items -> the
+    same eleven arrays with a leading batch axis, per-point arrays padded to ``Nmax1 = max(n1)`` (cloud 1 and everything indexed by
+    its points) / ``Nmax2 = max(n2)`` (cloud 2), plus ``n1``, ``n2`` (B,) int32.  Padding repeats the sample's FIRST point (and its
+    label / mask / radar_u / radar_v / opt_flow row): coordinates stay in range and an accidental read finds a real point.
+    -> (pc1 (B,Nmax1,3), pc2 (B,Nmax2,3), ft1, ft2, trans (B,4,4), labels (B,Nmax1,3), mask (B,Nmax1), interval (B),
+        radar_u (B,Nmax1), radar_v (B,Nmax1), opt_flow (B,Nmax1,2), n1, n2) as torch CPU tensors."""
+    if len(items) == 0:
+        raise ValueError("collate_ragged: empty batch")
+    n1 = np.array([np.asarray(it[0]).shape[0] for it in items], dtype=np.int32)
+    n2 = np.array([np.asarray(it[1]).shape[0] for it in items], dtype=np.int32)
+    if n1.min() < 1 or n2.min() < 1:
+        raise ValueError("collate_ragged: a frame without points")
+    m1, m2 = int(n1.max()), int(n2.max())
+
+    def pad(k, nmax, dtype=np.float32):
+        out = []
+        for it in items:
+            a = np.asarray(it[k]).astype(dtype)
+            out.append(np.concatenate([a, np.repeat(a[:1], nmax - a.shape[0], axis=0)], axis=0))
+        return torch.from_numpy(np.stack(out))
+
+    fixed = lambda k: torch.from_numpy(np.stack([np.asarray(it[k], dtype=np.float32) for it in items]))
+    return (pad(0, m1), pad(1, m2), pad(2, m1), pad(3, m2), fixed(4), pad(5, m1), pad(6, m1), fixed(7), pad(8, m1), pad(9, m1),
+            pad(10, m1), torch.from_numpy(n1), torch.from_numpy(n2))
+
+
+def extract_data_info_ragged(data, device="cuda"):
+    """extract_data_info (main_util.py:21-36) for a ``collate_ragged`` batch -> model-layout device tensors
+    (pc1, ft1 (B,3,Nmax1); pc2, ft2 (B,3,Nmax2); trans (B,4,4); gt (B,Nmax1,3); mask (B,Nmax1); interval (B); radar_u/v (B,Nmax1);
+    opt_flow (B,Nmax1,2); n1, n2 (B,) int32): the tuple of extract_data_info followed by the two count tensors."""
+    return (*extract_data_info(data[:11], device=device), torch.as_tensor(data[11]).to(device=device, dtype=torch.int32),
+            torch.as_tensor(data[12]).to(device=device, dtype=torch.int32))
 
 
 def as_batch_dict(info):

@@ -21,16 +21,21 @@ def _f32(t):
     return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
-def _metrics(B, N, dev, pc=None, pred=None, labels=None, mask=None, pred_m=None, gt_trans=None, pred_trans=None, res=None):
+def _metrics(B, N, dev, pc=None, pred=None, labels=None, mask=None, pred_m=None, gt_trans=None, pred_trans=None, res=None, npoints=None):
+    """npoints ((B,) int32 on the device): ragged samples -- per-sample metrics over the valid points, then their mean
+    (cmf_eval_metrics_counted); None: the dense batch, points pooled (cmf_eval_metrics)."""
     f32 = torch.float32
     pc, pred, labels, mask, pred_m, gt_trans, pred_trans = map(_f32, (pc, pred, labels, mask, pred_m, gt_trans, pred_trans))
     out = torch.empty(14, dtype=torch.float64, device=dev)
     ws = torch.empty(16 * B, dtype=torch.float64, device=dev)
     res = res or VOD_RADAR_RES
     ptr = lambda t: _lib.dev_ptr(t, f32)
-    _lib.check(_lib.lib().cmf_eval_metrics(B, N, ptr(pc), ptr(pred), ptr(labels), ptr(mask), ptr(pred_m), ptr(gt_trans),
-                                           ptr(pred_trans), res['r_res'], res['theta_res'], res['phi_res'],
-                                           out.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "cmf_eval_metrics")
+    tail = (ptr(pc), ptr(pred), ptr(labels), ptr(mask), ptr(pred_m), ptr(gt_trans), ptr(pred_trans), res['r_res'], res['theta_res'],
+            res['phi_res'], out.data_ptr(), ws.data_ptr(), _lib.stream_ptr())
+    if npoints is None:
+        _lib.check(_lib.lib().cmf_eval_metrics(B, N, *tail), "cmf_eval_metrics")
+    else:
+        _lib.check(_lib.lib().cmf_eval_metrics_counted(B, N, _lib.dev_ptr(npoints.contiguous(), torch.int32), *tail), "cmf_eval_metrics_counted")
     return out
 
 
@@ -58,5 +63,17 @@ def eval_batch(pc, pred, labels, mask, pred_m, gt_trans, pred_trans, args=None):
     """All three groups of main_util.py:175-192 from one kernel call -> (sf_metric, seg_metric, pose_metric)."""
     B, _, N = pc.shape
     m = _metrics(B, N, pc.device, pc, pred, labels, mask, pred_m, gt_trans, pred_trans, getattr(args, "radar_res", None))
+    return ({k: m[i] for i, k in enumerate(SF_KEYS)}, {k: m[9 + i] for i, k in enumerate(SEG_KEYS)},
+            {k: m[12 + i] for i, k in enumerate(POSE_KEYS)})
+
+
+def eval_batch_ragged(pc, pred, labels, mask, pred_m, gt_trans, pred_trans, npoints, args=None):
+    """eval_batch for a RAGGED batch (``CMFlow.forward_ragged``): pc (B,3,Nmax), pred, labels (B,Nmax,3), mask, pred_m (B,Nmax) padded,
+    npoints (B,) int32 on the device.  Every sample is evaluated on its own valid points and the B results are averaged -- what
+    main_util.py:176-192 accumulates when the loader's batch size is 1 (main.py:203), i.e. the reference's published protocol; NOT the
+    pooled-over-the-batch numbers eval_batch gives for a dense batch (cmf_eval_metrics_counted, csrc/eval.hip).  As there, a sample
+    without static points makes 'stat_rne' (and '50-50 rne') NaN.  -> (sf_metric, seg_metric, pose_metric)."""
+    B, _, N = pc.shape
+    m = _metrics(B, N, pc.device, pc, pred, labels, mask, pred_m, gt_trans, pred_trans, getattr(args, "radar_res", None), npoints=npoints)
     return ({k: m[i] for i, k in enumerate(SF_KEYS)}, {k: m[9 + i] for i, k in enumerate(SEG_KEYS)},
             {k: m[12 + i] for i, k in enumerate(POSE_KEYS)})

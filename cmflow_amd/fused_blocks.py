@@ -1088,9 +1088,10 @@ class EncoderPlan:
         return None
 
 
-def _multi_call(backward, n, plan, sp, streams, main):
+def _multi_call(backward, n, plan, sp, streams, main, counts=None):
     """Issue the n chains of a plan on their streams, forked from and joined back into `main` with torch stream waits around
-    cmf_setconv_*_multi."""
+    cmf_setconv_*_multi.  counts (forward, inference): (B,) int32 point counts of ragged samples -- the ball queries of all blocks are
+    then the counted nested query (cmf_setconv_queries_counted), whatever NESTED_QUERIES says: a block's own query is not counted."""
     import ctypes
     # The per-point tails of the n blocks (three <= 64-channel layers over the B*N points: latency, not work) run as batched
     # launches on the caller's stream -- behind the joined chains in forward, in front of the fork in backward; the chains on
@@ -1099,7 +1100,15 @@ def _multi_call(backward, n, plan, sp, streams, main):
     if backward:
         _lib.check(L().cmf_setconv_tail_backward(n, descs, main.cuda_stream), "cmf_setconv_tail_backward")
         stress_point([main])                    # (tests) between the tails and the bodies that consume their gradients
-    elif NESTED_QUERIES:
+    elif counts is not None:
+        cp = (ctypes.c_void_p * n)(*([_lib.dev_ptr(counts, torch.int32)] * n))
+        _lib.check(L().cmf_setconv_queries_counted(n, descs, ctypes.addressof(cp), main.cuda_stream), "cmf_setconv_queries_counted")
+        for i in range(n):
+            plan.descs[i].idx_ready = 1
+    elif not NESTED_QUERIES:
+        for i in range(n):                      # a plan serves dense and ragged calls: every forward call states who issues the queries
+            plan.descs[i].idx_ready = 0
+    else:
         # the ball queries of all n blocks as ONE launch per encoder call (nested radii over the same centres; both clouds of the first
         # encoder), on the caller's stream in front of the fork -- the chains then start at their first layer
         _lib.check(L().cmf_setconv_queries(n, descs, main.cuda_stream), "cmf_setconv_queries")
@@ -1160,7 +1169,10 @@ class MultiScaleBlockFn(Function):
     the parameters are not even autograd inputs of the node.  Numerics: same kernels per scale as SetConvBlockFn."""
 
     @staticmethod
-    def forward(ctx, xyz_t, y_all, plan, streams, sink_mode, *params):
+    def forward(ctx, xyz_t, y_all, plan, streams, sink_mode, counts, *params):
+        """counts: None, or (inference only) the (B,) int32 point counts of RAGGED samples on the device -- xyz_t / y_all are then padded
+        to N rows per sample and the blocks run behind the counted nested ball query (_multi_call): neighbours of a valid point are
+        points of its own sample below its count, a padded point's neighbour is point 0 of its sample."""
         import ctypes
         B, N, _ = xyz_t.shape
         n, co, dev = plan.n, plan.co, xyz_t.device
@@ -1179,7 +1191,7 @@ class MultiScaleBlockFn(Function):
             d.out, d.ldo = out_all.data_ptr() + 4 * i * co, n * co
             d.inference = inference
         sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
-        _multi_call(False, n, plan, sp, streams, main)
+        _multi_call(False, n, plan, sp, streams, main, counts=counts)
         _tap_indices(plan, saved, range(n))
         ctx.plan, ctx.keep, ctx.streams, ctx.sink_mode = plan, (xyz_t, y_all, saved), streams, sink_mode
         return out_all.view(B, N, n * co)
@@ -1239,7 +1251,7 @@ class MultiScaleBlockFn(Function):
             raise RuntimeError("parameter .grad buffers disappeared between forward and backward")
         sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
         _multi_call(True, n, plan, sp, streams, main)
-        return (None, dy_all, None, None, None, *(() if ctx.sink_mode else grads))
+        return (None, dy_all, None, None, None, None, *(() if ctx.sink_mode else grads))
 
 
 class DualCloudBlockFn(Function):
@@ -1338,11 +1350,18 @@ def set_conv_params(module):
     return params, [b[0], b[1], b[2], b2[0], b2[1], b2[2]]
 
 
-def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all):
-    """modules: the PointLocalFeature scales; y_all (B,N,len*O1) the stacked hoisted first-conv features."""
+def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all, counts=None):
+    """modules: the PointLocalFeature scales; y_all (B,N,len*O1) the stacked hoisted first-conv features.
+    counts ((B,) int32 on the device): RAGGED samples padded to N rows, inference only (eval-mode BatchNorm is row-wise; under
+    torch.no_grad()), N <= 1024 (the counted one-scan ball query) -- refused otherwise rather than sent down an uncounted path."""
     B, N, _ = xyz_t.shape
     o1 = y_all.shape[2] // len(modules)
     training = modules[0].mlp_bns[0].training
+    if counts is not None:
+        if training or torch.is_grad_enabled():
+            raise RuntimeError("ragged set-conv blocks are inference only (eval-mode BatchNorm, torch.no_grad())")
+        if N > 1024:
+            raise ValueError("ragged batches cover clouds of up to 1024 points (the counted one-scan ball query); got Nmax = %d" % N)
     key = (B, N, o1, bool(training), str(xyz_t.device), 1)
     plans = encoder.__dict__.setdefault("_plans", {})
     plan = plans.get(key)
@@ -1354,7 +1373,7 @@ def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all):
     if sink_mode and not y_all.requires_grad:
         # the node must exist for the parameter gradients even when the input features carry none (first encoder)
         y_all = y_all.detach().requires_grad_(True)
-    return MultiScaleBlockFn.apply(xyz_t, y_all, plan, streams, sink_mode, *params)
+    return MultiScaleBlockFn.apply(xyz_t, y_all, plan, streams, sink_mode, counts, *params)
 
 
 def set_conv(module, xyz_t, y):
@@ -1574,3 +1593,15 @@ class GlobalMaxCatFn(Function):
 
 def global_max_cat(f):
     return GlobalMaxCatFn.apply(f)
+
+
+def global_max_cat_counted(f, counts, want_arg=False):
+    """global_max_cat over RAGGED samples (inference): f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows
+    below each sample's count (cmf_global_max_cat_counted); want_arg: also the (B,C) int32 first row attaining it."""
+    B, N, C = f.shape
+    f = f.contiguous()
+    out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
+    arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
+    _lib.check(L().cmf_global_max_cat_counted(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.dev_ptr(counts, torch.int32),
+                                              _lib.stream_ptr()), "cmf_global_max_cat_counted")
+    return (out, arg) if want_arg else out

@@ -66,6 +66,40 @@ def knn_point(nsample, xyz, new_xyz, return_dist=False, i32=False):
     return (idx.long(), dist) if return_dist else idx.long()
 
 
+def knn_point_counted(nsample, xyz, new_xyz, n_src, return_dist=False):
+    """knn_point over RAGGED samples: xyz (B,Nmax,3) padded database with n_src (B,) int32 valid rows per sample, new_xyz (B,S,3)
+    -> (B,S,nsample) int32, canonical order, candidates below the sample's count only (cmf_knn_counted)."""
+    xyz = xyz.detach().contiguous()
+    new_xyz = new_xyz.detach().contiguous()
+    B, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    idx = torch.empty(B, S, nsample, dtype=_i32, device=xyz.device)
+    dist = torch.empty(B, S, nsample, dtype=_f32, device=xyz.device) if return_dist else None
+    err = _lib.lib().cmf_knn_counted(B, N, S, nsample, _lib.dev_ptr(xyz, _f32), _lib.dev_ptr(new_xyz, _f32), _lib.dev_ptr(n_src, _i32),
+                                     _lib.dev_ptr(idx, _i32), _lib.dev_ptr(dist, _f32), _lib.stream_ptr())
+    _lib.check(err, "cmf_knn_counted")
+    return (idx, dist) if return_dist else idx
+
+
+def ego_refine_counted(flow, pc1, score, counts, eps, thres):
+    """ego_refine over RAGGED samples (inference): flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
+    (pre_trans (b,4,4), sf_agg (b,3,Nmax), mask (b,Nmax) bool, stat (b,Nmax)): the solve over each sample's valid points
+    (cmf_ego_refine_counted: bit-identical to the dense call on the truncated sample); padded slots: flow 0, mask False, stat 0."""
+    flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
+    b, _, n = pc1.shape
+    dev = pc1.device
+    W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
+    trans = torch.empty(b, 4, 4, dtype=_f32, device=dev)
+    sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
+    stat = torch.empty(b, n, dtype=_f32, device=dev)
+    err = _lib.lib().cmf_ego_refine_counted(b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32),
+                                            _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32),
+                                            _lib.dev_ptr(trans, _f32), None, _lib.dev_ptr(sf, _f32), mask.data_ptr(), _lib.dev_ptr(stat, _f32),
+                                            _lib.stream_ptr())
+    _lib.check(err, "cmf_ego_refine_counted")
+    return trans, sf, mask.view(torch.bool), stat
+
+
 def rel_xyz(xyz_t, centre_t, idx):
     """(B,N,3) points, (B,P,3) centres, idx (B,P,S) int32 -> (B,P,S,4): neighbour minus centre with a zero fourth column
     (radarflow_util.py:207-208 + the row padding of the narrow GEMMs), one launch.  No gradient (coordinates are inputs)."""
@@ -226,6 +260,17 @@ class MultiScaleEncoder(nn.Module):
             main.wait_stream(st)
         return torch.cat(outs, dim=2)
 
+    def forward_pm_ragged(self, xyz_t, feats, counts, n_tail=0):
+        """forward_pm over RAGGED samples (inference): xyz_t (B,Nmax,3), feats (B,Nmax,C) padded, counts (B,) int32 on the device.
+        The stacked first conv is row-wise and runs on all rows; the blocks run behind the counted nested ball query."""
+        if not (FB.USE_BLOCK_CALLS and feats.shape[2] % 4 == 0):
+            raise RuntimeError("the ragged encoder runs on the block calls (rows of a multiple of 4 floats)")
+        B, N, Kp = feats.shape
+        y_all = FB.StackedFirstConvFn.apply(feats.reshape(B * N, Kp), n_tail, 0, *[sa.mlp_convs[0].weight for sa in self.ms_ls]).view(B, N, -1)
+        if self._streams is None:
+            self._streams = FB.scale_streams(len(self.ms_ls))
+        return FB.multi_scale_set_conv(self, list(self.ms_ls), self._streams, xyz_t, y_all, counts)
+
     threaded_enqueue = True
     def forward_pm_pair(self, xyz1_t, feats1, xyz2_t, feats2):
         """Two calls of this (weight-shared) encoder -- forward_pm(xyz1_t, feats1), forward_pm(xyz2_t, feats2) in this
@@ -385,15 +430,18 @@ class FeatureCorrelator(nn.Module):
         """Reference contract (:185-237): xyz (B,3,N), points (B,D,N) -> patch-to-patch cost (B,mlp[-1],N1)."""
         return self.forward_pm(_rows(xyz1), _rows(xyz2), _rows(points1), _rows(points2)).transpose(1, 2)
 
-    def forward_pm(self, xyz1_t, xyz2_t, f1, f2):
+    def forward_pm(self, xyz1_t, xyz2_t, f1, f2, n1=None, n2=None):
         """Point-major cost volume.  xyz*_t (B,N,3), f1/f2 (B,N,D) -> (B,N,512).  The first conv
-        over cat[f1, f2[idx], dxyz] is split by linearity into per-point GEMMs."""
+        over cat[f1, f2[idx], dxyz] is split by linearity into per-point GEMMs.
+        n1, n2 ((B,) int32, inference): ragged samples -- both neighbour searches take candidates below the sample's count only."""
         assert not self.bn
-        return self._forward_blocks(xyz1_t, xyz2_t, f1, f2)
+        return self._forward_blocks(xyz1_t, xyz2_t, f1, f2, n1, n2)
 
 
-def _fc_blocks(self, xyz1_t, xyz2_t, f1, f2):
+def _fc_blocks(self, xyz1_t, xyz2_t, f1, f2, n1=None, n2=None):
     """FeatureCorrelator on the fused blocks (own GEMMs, hoisted first conv, fused grouping)."""
+    knn2 = (lambda: knn_point(K, xyz2_t, xyz1_t, i32=True)) if n2 is None else (lambda: knn_point_counted(K, xyz2_t, xyz1_t, n2))
+    knn1 = (lambda: knn_point(K, xyz1_t, xyz1_t, i32=True)) if n1 is None else (lambda: knn_point_counted(K, xyz1_t, xyz1_t, n1))
     D1, D2 = f1.shape[2], f2.shape[2]
     K = self.nsample
     c0, c1, c2 = self.mlp_convs
@@ -409,10 +457,10 @@ def _fc_blocks(self, xyz1_t, xyz2_t, f1, f2):
             st.wait_stream(main)
         FB.stress_point(list(side) + [main])
     with torch.cuda.stream(side[0]) if side else contextlib.nullcontext():
-        nbr = Neighbors(knn_point(K, xyz2_t, xyz1_t, i32=True), xyz2_t.shape[1])     # needed after p1: off the main stream too
+        nbr = Neighbors(knn2(), xyz2_t.shape[1])                                     # needed after p1: off the main stream too
         p2 = FB.stress_mark(FB.linear(f2, w0[:, D1:D1 + D2]))
     with torch.cuda.stream(side[1]) if side else contextlib.nullcontext():
-        nbr2 = Neighbors(knn_point(K, xyz1_t, xyz1_t, i32=True), xyz1_t.shape[1])
+        nbr2 = Neighbors(knn1(), xyz1_t.shape[1])
         dxyz2 = rel_xyz(xyz1_t, xyz1_t, nbr2.idx)
         h2 = FB.stress_mark(self.weightnet2.hidden_pm(dxyz2))
     p1 = FB.linear(f1, w0[:, :D1], c0.bias)

@@ -65,3 +65,9 @@ class RaFlow(CMFlow):
         output = self.ROFE_module(pc1, pc2, feature1, feature2)
         sf_agg, pre_trans, mask_s = self.SFR_module(output, pc1, feature1, interval)
         return output, sf_agg, pre_trans, mask_s
+
+    def forward_ragged(self, *args, **kwargs):
+        """Not provided: the SFR module (models/raflow.py, static-flow refinement) divides by the point count N in three places and
+        votes over all points of a sample; a counted form of it is a different piece of work from CMFlow's (cmflow.CMFlow.forward_ragged)."""
+        raise NotImplementedError("RaFlow has no ragged-batch forward: its SFR module normalises by the padded point count; "
+                                  "run RaFlow one frame pair per call (forward at B = 1)")

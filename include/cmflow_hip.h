@@ -631,6 +631,47 @@ int cmf_pseudo_labels(int b, int n, const float *pc1, const float *gt_trans, con
  * the side-stream chains at every fork point (fused_blocks.stress_*): results must not depend on it. */
 int cmf_debug_spin(float microseconds, void *stream);
 
+/* ---- ragged batches: B samples of their own point counts in one call (inference) ------------------------------------
+ * The reference evaluates on the WHOLE cloud of every frame (dataset/vod.py:92-111 resamples for training only), one frame pair per
+ * forward (main.py:203: batch_size = 1), N1 != N2.  Here a batch of such pairs is a padded (B, Nmax, .) tensor plus per-sample counts
+ * in DEVICE memory (const int *, B entries); the counted forms below are the five places where a sample's size enters the
+ * arithmetic.  Everything else of the eval-mode model is row-wise and runs on the padded rows unchanged.  Every counted form equals
+ * its dense entry point called with b = 1 on the truncated sample (rows [0, count)), in the strength stated per function; counts are
+ * clamped to [0, rows in memory] inside the kernels, so a wrong count cannot make them leave the padded tensors; a count of 0 (a
+ * caller's error: a sample has at least one point) is not finite garbage but NaN / -inf -- the weights divide by a zero score sum, the
+ * maximum of no rows is -inf.  Padded input rows must be finite; they never influence a valid output.
+ *
+ * cmf_ball_query_multi_counted: cmf_ball_query_multi with candidates j < n_src[c][s] and centres p < n_ctr[c][s] (tables of nclouds
+ *   device pointers, host arrays).  Valid centres: bit-identical to cmf_ball_query(b = 1, n = n_src, m = n_ctr) per scale; the rows of
+ *   padded centres and of empty balls are zeros.  n <= 1024 (the one-scan kernel); larger clouds are refused, not sent elsewhere.
+ * cmf_setconv_queries_counted: cmf_setconv_queries over ragged samples, counts[i] the count array of block i (centres = cloud in a
+ *   set-conv block; the blocks of one cloud must share one array).  Refuses N > 1024.
+ * cmf_knn_counted: cmf_knn with candidates j < n_src[s]; canonical order; indices (and distances) bit-identical to
+ *   cmf_knn(b = 1, n = n_src[s]) for every query row, padded query rows included (their lists are valid rows of their own sample).
+ * cmf_global_max_cat_counted: maximum and arg over the rows < cnt[s], bit-identical to the dense call on the truncated sample; ALL N
+ *   rows of out are written (copy | that maximum).
+ * cmf_ego_refine_counted: score sum, weights, weighted centroids, covariance over the rows < cnt[s] in the dense kernel's order:
+ *   trans, aux and the valid slices of W, Bm, sf, mask are bit-identical to cmf_ego_refine(b = 1, n = cnt[s]); padded slots of W, Bm,
+ *   sf, mask are zeros.  stat (b,n), optional: score with the padded slots zeroed.
+ * cmf_eval_metrics_counted: per sample the 14 metrics of cmf_eval_metrics(b = 1, n = cnt[s]) on its valid rows, then their mean over
+ *   the samples in index order -- what main_util.py:176-192 accumulates with the test loader's batch size 1.  A sample without
+ *   static points gives stat_rne = NaN (0 / 0, numpy's mean of an empty selection) and so does the mean; a sample without moving
+ *   points gives mov_rne = 0 (0 / 1e-6): both exactly as cmf_eval_metrics at b = 1.  workspace: 16 * B doubles. */
+int cmf_ball_query_multi_counted(int b, int n, int m, int nq, const float *radii, const int *nsamples, int nclouds,
+                                 const float *const *new_xyz, const float *const *xyz, int *const *idx,
+                                 const int *const *n_ctr, const int *const *n_src, void *stream);
+int cmf_setconv_queries_counted(int n, const cmf_setconv_desc *descs, const int *const *counts, void *stream);
+int cmf_knn_counted(int b, int n, int s, int nsample, const float *xyz, const float *new_xyz, const int *n_src,
+                    int *idx, float *dist, void *stream);
+int cmf_global_max_cat_counted(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg,
+                               const int *cnt, void *stream);
+int cmf_ego_refine_counted(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score,
+                           const int *cnt, float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask,
+                           float *stat, void *stream);
+int cmf_eval_metrics_counted(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
+                             const float *pred_m, const float *gt_trans, const float *pred_trans,
+                             float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
