@@ -54,7 +54,7 @@ SIGNATURES = {
     "cmf_gemm_profile_eligible": [_vp, _vp],
     "cmf_gemm_profile_end": [_vp, _vp, _vp, _vp, _vp],
     "cmf_gemm_profile_records": [_vp, _ll],
-    "cmf_setconv_sizes": [_vp, _vp, _vp, _vp],
+    "cmf_setconv_sizes": [_vp, _vp, _vp, _vp, _vp],
     "cmf_setconv_forward": [_vp, _vp],
     "cmf_setconv_backward": [_vp, _vp],
     "cmf_setconv_bn_offsets": [_vp, _vp],
@@ -62,8 +62,6 @@ SIGNATURES = {
     "cmf_mlp_forward": [_vp, _vp],
     "cmf_mlp_backward": [_vp, _vp],
     "cmf_bn_running_update": [_ci, _vp, _ci, _vp, _vp, _vp],
-    "cmf_setconv_forward_multi": [_ci, _vp, _vp],
-    "cmf_setconv_backward_multi": [_ci, _vp, _vp],
     "cmf_setconv_forward_heads_multi": [_ci, _vp, _vp],
     "cmf_setconv_forward_bodies_batched": [_ci, _vp],
     "cmf_setconv_backward_bodies_batched": [_ci, _vp],
@@ -124,7 +122,6 @@ SIGNATURES = {
     "cmf_unstack_first_conv_grad": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp],
     "cmf_global_max_cat_grad": [_ci, _ci, _ci, _vp, _ll, _vp, _vp, _ll, _vp],
     "cmf_mem_stats": [],
-    "cmf_radar_loss_workspace": [_ci, _ci],
     "cmf_radar_loss_workspace_nb": [_ci, _ci, _ci],
     "cmf_radar_loss_workspace_tiled": [_ci, _ci, _ci],
     "cmf_radar_loss": [_vp, _vp],
@@ -133,7 +130,7 @@ SIGNATURES = {
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }
-RESTYPES = {"cmf_mem_stats": _ll, "cmf_radar_loss_workspace": _ll, "cmf_radar_loss_workspace_nb": _ll, "cmf_radar_loss_workspace_tiled": _ll, "cmf_gemm_trace_read": _ll, "cmf_gemm_profile_records": _ll}
+RESTYPES = {"cmf_mem_stats": _ll, "cmf_radar_loss_workspace_nb": _ll, "cmf_radar_loss_workspace_tiled": _ll, "cmf_gemm_trace_read": _ll, "cmf_gemm_profile_records": _ll}
 
 
 class GemmLaunchRecord(ctypes.Structure):

@@ -794,8 +794,6 @@ extern "C" long long cmf_radar_loss_workspace_nb(int b, int n, int num_nb)
     return (head + 3) / 4 * 4 + (long long)b * (long long)lg_sample_floats(n, lg_nb_ok(num_nb) ? num_nb : 16);
 }
 
-extern "C" long long cmf_radar_loss_workspace(int b, int n) { return cmf_radar_loss_workspace_nb(b, n, LS_NB); }
-
 extern "C" long long cmf_radar_loss_workspace_tiled(int b, int n, int num_nb)
 {
     const long long head = 4 + (long long)b * LS_PARTIALS;

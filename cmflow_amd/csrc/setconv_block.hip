@@ -100,11 +100,13 @@ inline int chan(const cmf_setconv_desc *d, int layer)       // out channels of B
 // (gather_layout: the second encoder's shapes) keeps in that tensor's slot of `saved` only what the gathering GEMMs read -- M row
 // indices and the three coordinate planes of Wx -- instead of M x O1 floats (1 GB at the largest scale, B = 64); and the slot of
 // the data gradient into that layer in the backward scratch holds, when the gradient is summed inside the GEMM
-// (gather_sum_layout: an input gradient is wanted, d->dy set), the pieces matrix, the permutation, the permuted source points
-// and relative coordinates.  Both predicates are pure functions of the descriptor's SHAPE fields (and of d->dy being set or
-// not for the second): cmf_setconv_sizes, the forward and the backward call must agree on them, so the pointer-alignment
+// (gather_sum_shape and an input gradient wanted: make_layout's sum_in_gemm), the pieces matrix, the permutation, the permuted
+// source points and relative coordinates.  Both predicates are pure functions of the descriptor's SHAPE fields:
+// cmf_setconv_sizes, the forward and the backward call must agree on them, so the pointer-alignment
 // conditions of the gathering kernels are NOT part of them -- a block with the compact layout and a misaligned y is refused
-// (CMF_CHECK_ARG in the calls) instead of overrunning a slot that was never sized for the materialised tensor.
+// (CMF_CHECK_ARG in the calls) instead of overrunning a slot that was never sized for the materialised tensor.  Whether a
+// backward call wants the input gradient (d->dy set) is the CALL's business: the backward entry points pass it to make_layout,
+// cmf_setconv_sizes reports the scratch size of either case and reads no output pointer.
 // CMF_TRAIN_GATHER=0 / CMF_TRAIN_GATHER_SUM=0 (A/B) bring the materialised sizes back.
 inline bool gather_layout(const cmf_setconv_desc *d)
 {
@@ -112,11 +114,12 @@ inline bool gather_layout(const cmf_setconv_desc *d)
     const long long M = (long long)d->B * d->N * d->S;
     return on && M % 128 == 0 && M < (1ll << 31) && d->C[0] % 128 == 0 && d->O1 % 128 == 0 && d->ldy % 4 == 0;
 }
-inline bool gather_sum_layout(const cmf_setconv_desc *d)
+inline bool gather_sum_shape(const cmf_setconv_desc *d)
 {
     static const bool on = !(getenv("CMF_TRAIN_GATHER_SUM") && getenv("CMF_TRAIN_GATHER_SUM")[0] == '0');
-    return on && gather_layout(d) && d->dy != nullptr && d->S >= 2;
+    return on && gather_layout(d) && d->S >= 2;
 }
+inline bool gather_sum_layout(const cmf_setconv_desc *d) { return gather_sum_shape(d) && d->dy != nullptr; }   // of a backward call
 
 // BN backward of the layer behind the gathered first layer inside its weight-gradient GEMM (cmf_gemm_dw_gather_bn_bwd): the stand-alone
 // pass over (M, C2) -- read dU, read Z, write dZ: 3 GB per step at B = 64 -- goes, dZ lands in a buffer of its own for the data-gradient
@@ -130,7 +133,9 @@ inline bool bnb_gather(const cmf_setconv_desc *d)
     return on && d->training && gather_layout(d) && ((long long)d->B * d->N * d->S) >= 32768;
 }
 
-Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool backward)
+// sum_in_gemm (backward only): the call produces the input gradient, so a gather_sum_shape block sums the first layer's data gradient
+// inside the GEMM and its dU1 slot is the compact one
+Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool backward, bool sum_in_gemm = false)
 {
     Layout L;
     const long long P = (long long)d->B * d->N, M = P * d->S;
@@ -166,7 +171,7 @@ Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool
         L.dU3 = t.take(M * C3);
         L.dU2 = t.take(M * C2);
         // (summed inside the GEMM: pieces (P + M/64) x O1 | perm M | source points M | relative coordinates 4 M -- sum_slots below)
-        L.dU1 = t.take(gather_sum_layout(d) ? (size_t)(P + M / 64) * O1 + 6 * (size_t)M : (size_t)M * O1);
+        L.dU1 = t.take(sum_in_gemm && gather_sum_shape(d) ? (size_t)(P + M / 64) * O1 + 6 * (size_t)M : (size_t)M * O1);
         L.dZ2 = bnb_gather(d) ? t.take(M * C2) : nullptr;
         size_t sk = 0;
         sk = std::max(sk, (size_t)dw_split(P, C6, C5) * C6 * C5);
@@ -392,14 +397,16 @@ int bwd_layer1_gather(const cmf_setconv_desc *d, const Layout &L, long long M, i
 
 }  // namespace
 
-extern "C" int cmf_setconv_sizes(const cmf_setconv_desc *d, long long *saved_floats, long long *scratch_fwd, long long *scratch_bwd)
+extern "C" int cmf_setconv_sizes(const cmf_setconv_desc *d, long long *saved_floats, long long *scratch_fwd, long long *scratch_bwd,
+                                 long long *scratch_bwd_input_grad)
 {
     CMF_CHECK_ARG(d && d->B > 0 && d->N > 0 && d->S > 0 && d->S <= 64 && d->O1 % 4 == 0);
     for (int i = 0; i < 5; ++i) CMF_CHECK_ARG(d->C[i] > 0 && d->C[i] % 4 == 0);
-    Layout f = make_layout(d, nullptr, nullptr, false), b = make_layout(d, nullptr, nullptr, true);
+    const Layout f = make_layout(d, nullptr, nullptr, false);
     if (saved_floats) *saved_floats = (long long)f.saved_floats;
     if (scratch_fwd) *scratch_fwd = (long long)f.scratch_floats;
-    if (scratch_bwd) *scratch_bwd = (long long)b.scratch_floats;
+    if (scratch_bwd) *scratch_bwd = (long long)make_layout(d, nullptr, nullptr, true, false).scratch_floats;
+    if (scratch_bwd_input_grad) *scratch_bwd_input_grad = (long long)make_layout(d, nullptr, nullptr, true, true).scratch_floats;
     return 0;
 }
 
@@ -629,7 +636,7 @@ extern "C" int cmf_setconv_tail_backward(int n, const cmf_setconv_desc *descs, v
     if (!tail_batchable(n, descs)) {
         for (int i = 0; i < n; ++i) {
             const cmf_setconv_desc *d = &descs[i];
-            const Layout L = make_layout(d, d->saved, d->scratch, true);
+            const Layout L = make_layout(d, d->saved, d->scratch, true, d->dy != nullptr);
             const long long P = (long long)d->B * d->N;
             const int C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
             const float *b5 = L.bn[5];
@@ -641,7 +648,7 @@ extern "C" int cmf_setconv_tail_backward(int n, const cmf_setconv_desc *descs, v
         return 0;
     }
     Layout L[CMF_MAX_BATCH];
-    for (int i = 0; i < n; ++i) L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true);
+    for (int i = 0; i < n; ++i) L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true, descs[i].dy != nullptr);
     const bool training = descs[0].training != 0;
     {
         CmfActBwdArgs a[CMF_MAX_BATCH];
@@ -690,7 +697,7 @@ static int setconv_backward_part(const cmf_setconv_desc *d, void *st, int part)
 {
     CMF_CHECK_ARG(d && d->xyz && d->saved && d->scratch && d->dout);
     CMF_CHECK_ARG(!gather_layout(d) || (d->y && gather_operands_aligned(d)));
-    const Layout L = make_layout(d, d->saved, d->scratch, true);
+    const Layout L = make_layout(d, d->saved, d->scratch, true, d->dy != nullptr);
     const long long P = (long long)d->B * d->N, M = P * d->S;
     const int O1 = d->O1, C2 = d->C[0], C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
     const float *b5 = L.bn[5], *b2 = L.bn[2];
@@ -879,16 +886,6 @@ static int setconv_multi(int n, const cmf_setconv_desc *descs, void *const *stre
     return 0;
 }
 
-extern "C" int cmf_setconv_forward_multi(int n, const cmf_setconv_desc *descs, void *const *streams)
-{
-    return setconv_multi(n, descs, streams, false);
-}
-
-extern "C" int cmf_setconv_backward_multi(int n, const cmf_setconv_desc *descs, void *const *streams)
-{
-    return setconv_multi(n, descs, streams, true);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // The slot-level bodies of up to CMF_MAX_BATCH NARROW blocks (the first encoder: 2 clouds x 4 scales, 32 / 32 / 64 channels) in lock
 // step: one batched launch per stage for all blocks instead of one kernel per block and stage on the stream pool.  At these widths
@@ -1038,7 +1035,7 @@ static int setconv_backward_bodies_batch(int n, const cmf_setconv_desc *descs_in
     Layout L[CMF_MAX_BATCH];
     for (int i = 0; i < n; ++i) {
         CMF_CHECK_ARG(descs[i].xyz && descs[i].saved && descs[i].scratch && descs[i].dout);
-        L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true);
+        L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true, descs[i].dy != nullptr);
     }
     const int O1 = descs[0].O1, C2 = descs[0].C[0], C3 = descs[0].C[1];
     const bool want_dy = descs[0].dy != nullptr, want_dwx = descs[0].dwx != nullptr;

@@ -12,6 +12,7 @@ Design (DESIGN.md "Fused path"):
   their epilogue; weight-gradient GEMMs contract over the positions with deterministic split-K and
   re-apply the producer's BN+ReLU to the saved Z in their B-operand prologue.
 """
+import ctypes
 import os
 
 import torch
@@ -79,6 +80,12 @@ _side_pool = {}
 
 
 SERIAL = False
+USE_BLOCK_CALLS = True                  # False: the Python-sequenced SetConvFn / MLPChainFn (the reference the block calls are tested against)
+NESTED_QUERIES = os.environ.get("CMF_NESTED_QUERIES", "1") != "0"       # 0: every block issues its own ball query (A/B)
+# Debug tap for tests: when a list, every multi-scale / dual-cloud forward call appends, per block, the ball-query indices the LIBRARY
+# issued (cmf_setconv_forward's first kernel; they sit at the head of the block's `saved` arena as int32 (B, N, S)):
+# (radius, nsample, idx clone).  None (default): nothing is copied.
+IDX_TAP = None
 
 
 def set_serial(net, on):
@@ -252,6 +259,16 @@ def grad_sink(t):
         col = t.storage_offset() - base.storage_offset()
         if t.shape[0] == rows and t.stride() == (K, 1) and 0 <= col and col + t.shape[1] <= K:
             return base.grad.view(rows, K)[:, col:col + t.shape[1]]
+    return None
+
+
+def _wx_sink(pwx, O1):
+    """grad_sink for wx, the [:, :3] view of a set-conv block's first conv weight (out, 3+C, 1, 1): the weight's whole gradient
+    buffer -- the kernels write its xyz columns with the row stride 3+C -- or None.  Needs no opt-in: a dense .grad is enough."""
+    base = pwx._base if pwx._base is not None else pwx
+    if base.is_leaf and base.grad is not None and base.grad.is_contiguous() and base.dim() == 4 and \
+            pwx.shape == (O1, 3) and pwx.storage_offset() == base.storage_offset():
+        return base.grad
     return None
 
 
@@ -503,7 +520,6 @@ class StackedFirstConvFn(Function):
 
     @staticmethod
     def forward(ctx, feats, n_tail, n_grad, *weights):
-        import ctypes
         M, Kp = feats.shape
         if StackedFirstConvFn._uniform(weights):                                 # one launch (cmf_stack_first_conv)
             o1, cin = weights[0].shape[0], weights[0].shape[1] - 3
@@ -542,7 +558,7 @@ class StackedFirstConvFn(Function):
         dwf = gemm_dw(dy, feats)                                                 # (n*O1, Kp)
         ws = ctx.weights
         if StackedFirstConvFn._uniform(ws) and all(w.is_leaf and w.grad is not None and w.grad.is_contiguous() for w in ws):
-            import ctypes                                                        # every scale owns a gradient buffer: one launch
+            # every scale owns a gradient buffer: one launch
             o1, cin = ws[0].shape[0], ws[0].shape[1] - 3
             ptrs = (ctypes.c_void_p * len(ws))(*[w.grad.data_ptr() for w in ws])
             _lib.check(L().cmf_unstack_first_conv_grad(len(ws), o1, cin, ctx.n_tail, Kp, dwf.data_ptr(), ctypes.addressof(ptrs),
@@ -588,14 +604,9 @@ def inputs_point_major(pc1, pc2, ft1, ft2):
     return x1, x2, a1, a2
 
 
-def _pad_k(t):
-    """Copy a 2-D tensor into a buffer whose row stride is a multiple of 4 floats (zero padded); returns the
-    (rows, K) view of it."""
-    return _pad_cols(t)[:, :t.shape[1]]
-
-
 def _pad_cols(t):
-    """Like _pad_k but returns the padded (rows, ld) tensor (extra zero columns participate harmlessly)."""
+    """Copy a 2-D tensor into a buffer whose row stride is a multiple of 4 floats; returns the padded (rows, ld) tensor (the extra
+    zero columns participate harmlessly)."""
     r, k = t.shape
     ld = (k + 3) // 4 * 4
     if ld == k and t.is_contiguous():
@@ -652,6 +663,53 @@ class MLPChainFn(Function):
         return (dx, None, None, *grads)
 
 
+# ---- block-call descriptors (cmf_mlp_desc / cmf_setconv_desc): the parts both fill the same way ------------------
+def _sizes(name, d, n):
+    """The n arena sizes (floats) of a block call: cmf_mlp_sizes / cmf_setconv_sizes."""
+    out = [ctypes.c_longlong() for _ in range(n)]
+    _lib.check(getattr(L(), name)(ctypes.addressof(d), *[ctypes.addressof(v) for v in out]), name)
+    return [v.value for v in out]
+
+
+def _row_major4(t):
+    """A 2-D gradient as the block calls read it: unit channel stride, rows a multiple of 4 floats apart."""
+    return t if (t.stride(1) == 1 and t.stride(0) % 4 == 0) else t.contiguous()
+
+
+def _fill_bn(d, l, bn, training, defer=False):
+    """BatchNorm layer l of a descriptor: hyper-parameters, affine parameters and running statistics.  defer: the call takes batch
+    statistics only and the running statistics are updated afterwards (cmf_bn_running_update)."""
+    assert bn.momentum is not None, "cumulative moving average BN is not supported by the block call"
+    d.eps[l], d.momentum[l] = bn.eps, bn.momentum
+    d.gamma[l], d.beta[l] = bn.weight.data_ptr(), bn.bias.data_ptr()
+    d.rmean[l], d.rvar[l] = (None, None) if defer else (bn.running_mean.data_ptr(), bn.running_var.data_ptr())
+    d.nbt[l] = bn.num_batches_tracked.data_ptr() if (training and bn.track_running_stats and not defer) else None
+
+
+def _param_sinks(params, bn_slots, O1=None):
+    """The gradient sink of every parameter of a block, None where it has none.  The two BN parameters of a layer share one accumulate
+    flag in the descriptors: they have their sinks together or not at all.  O1 given: params[0] is the wx of a set-conv block."""
+    sinks = [grad_sink(t) for t in params] if O1 is None else [_wx_sink(params[0], O1)] + [grad_sink(t) for t in params[1:]]
+    for _, k in bn_slots:
+        if sinks[k] is None or sinks[k + 1] is None:
+            sinks[k] = sinks[k + 1] = None
+    return sinks
+
+
+def _route_grads(d, params, dst, acc, w_slots, bn_slots):
+    """Point the parameter-gradient outputs of a descriptor at dst[k] (accumulated into if acc, else written) or, where dst[k] is
+    None, at a fresh tensor (written).  w_slots: (j, k) -- d.dw[j] is the gradient of params[k]; bn_slots: (l, k) -- d.dgamma[l] /
+    d.dbeta[l] are the gradients of params[k] / params[k + 1].
+    -> (the fresh tensors by parameter index, None elsewhere: what autograd must be handed; the destination of every gradient)."""
+    fresh = [None if s is not None else torch.empty_like(t, memory_format=torch.contiguous_format) for t, s in zip(params, dst)]
+    out = [f if s is None else s for f, s in zip(fresh, dst)]
+    for j, k in w_slots:
+        d.dw[j], d.acc_w[j] = out[k].data_ptr(), int(acc and fresh[k] is None)
+    for l, k in bn_slots:
+        d.dgamma[l], d.dbeta[l], d.acc_bn[l] = out[k].data_ptr(), out[k + 1].data_ptr(), int(acc and fresh[k] is None)
+    return fresh, out
+
+
 class MLPChainBlockFn(Function):
     """MLPChainFn with the kernel sequence issued by ONE C-ABI call per direction (cmf_mlp_forward / _backward,
     csrc/setconv_block.hip): same kernels, same order, same numerics.  Sequenced from Python the heads' chains were host
@@ -660,7 +718,6 @@ class MLPChainBlockFn(Function):
 
     @staticmethod
     def forward(ctx, x, bns, training, *params):
-        import ctypes
         x = x if (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else x.contiguous()
         M, dev, nl = x.shape[0], x.device, len(bns)
         d = _lib.MlpDesc()
@@ -670,26 +727,20 @@ class MLPChainBlockFn(Function):
         for l, bn in enumerate(bns):
             w = params[3 * l].contiguous()
             ws.append(w)
-            assert bn.momentum is not None, "cumulative moving average BN is not supported by the block call"
-            d.C[l + 1] = w.shape[0]
-            d.eps[l], d.momentum[l] = bn.eps, bn.momentum
-            d.w[l], d.gamma[l], d.beta[l] = w.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr()
-            d.rmean[l], d.rvar[l] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            d.nbt[l] = bn.num_batches_tracked.data_ptr() if (training and bn.track_running_stats) else None
-        n_s, n_f, n_b = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.check(L().cmf_mlp_sizes(ctypes.addressof(d), ctypes.addressof(n_s), ctypes.addressof(n_f), ctypes.addressof(n_b)), "cmf_mlp_sizes")
-        saved = torch.empty(n_s.value, dtype=_f32, device=dev)
-        scratch = torch.empty(n_f.value, dtype=_f32, device=dev)
+            d.C[l + 1], d.w[l] = w.shape[0], w.data_ptr()
+            _fill_bn(d, l, bn, training)
+        n_saved, n_fwd, n_bwd = _sizes("cmf_mlp_sizes", d, 3)
+        saved = torch.empty(n_saved, dtype=_f32, device=dev)
+        scratch = torch.empty(n_fwd, dtype=_f32, device=dev)
         out = torch.empty(M, ws[-1].shape[0], dtype=_f32, device=dev)
         d.x, d.ldx, d.saved, d.scratch, d.out, d.ldo = x.data_ptr(), x.stride(0), saved.data_ptr(), scratch.data_ptr(), out.data_ptr(), out.stride(0)
         _lib.check(L().cmf_mlp_forward(ctypes.addressof(d), _lib.stream_ptr()), "cmf_mlp_forward")
-        ctx.state = (d, x, ws, saved, n_b.value)
+        ctx.state = (d, x, ws, saved, n_bwd)
         ctx.params = params
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes
         d, x, ws, saved, n_bwd = ctx.state
         P = ctx.params
         dev = dy.device
@@ -697,20 +748,8 @@ class MLPChainBlockFn(Function):
             dy = dy.contiguous()
         scratch = torch.empty(n_bwd, dtype=_f32, device=dev)
         d.scratch, d.dout, d.lddout = scratch.data_ptr(), dy.data_ptr(), dy.stride(0)
-        grads = [None] * len(P)
-        for l in range(d.L):
-            sink = grad_sink(P[3 * l])
-            if sink is not None:
-                d.dw[l], d.acc_w[l] = sink.data_ptr(), 1
-            else:
-                grads[3 * l] = torch.empty_like(ws[l])
-                d.dw[l], d.acc_w[l] = grads[3 * l].data_ptr(), 0
-            sg, sb = grad_sink(P[3 * l + 1]), grad_sink(P[3 * l + 2])
-            if sg is not None and sb is not None:
-                d.dgamma[l], d.dbeta[l], d.acc_bn[l] = sg.data_ptr(), sb.data_ptr(), 1
-            else:
-                grads[3 * l + 1], grads[3 * l + 2] = torch.empty_like(P[3 * l + 1]), torch.empty_like(P[3 * l + 2])
-                d.dgamma[l], d.dbeta[l], d.acc_bn[l] = grads[3 * l + 1].data_ptr(), grads[3 * l + 2].data_ptr(), 0
+        w_slots, bn_slots = [(l, 3 * l) for l in range(d.L)], [(l, 3 * l + 1) for l in range(d.L)]
+        grads, _ = _route_grads(d, P, _param_sinks(P, bn_slots), True, w_slots, bn_slots)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape[0], x.shape[1], dtype=_f32, device=dev)
@@ -723,14 +762,7 @@ class MLPChainBlockFn(Function):
 
 def mlp_chain(x, layers, training):
     """layers: list of (conv, bn) modules.  x (..., K) -> (..., C_L)."""
-    shp = x.shape
-    params = []
-    for conv, bn in layers:
-        params += [conv.weight.view(conv.weight.shape[0], conv.weight.shape[1]), bn.weight, bn.bias]
-    block = USE_BLOCK_CALLS and len(layers) <= 4 and shp[-1] % 4 == 0 and all(c.weight.shape[0] % 4 == 0 for c, _ in layers)
-    fn = MLPChainBlockFn if block else MLPChainFn
-    y = fn.apply(x.reshape(-1, shp[-1]), [bn for _, bn in layers], training, *params)
-    return y.view(*shp[:-1], y.shape[-1])
+    return mlp_chain_w(x, [(conv.weight.view(conv.weight.shape[0], conv.weight.shape[1]), bn) for conv, bn in layers], training)
 
 
 def mlp_chain_w(x, layers, training):
@@ -807,17 +839,11 @@ class SetConvFn(Function):
         sums5 = colsum_n(part, O1, sb1, sg1)                 # [5][O1]: s1, s2, q0, q1, q2
         g["g1"], g["b1"] = (None if sg1 is not None else sums5[1]), (None if sb1 is not None else sums5[0])
         M = dU.shape[0]
-        # wx is the [:, :3] slice of the first conv's (out, 3+C) weight: accumulate into the same slice of its grad
-        wbase = pwx._base if pwx._base is not None else pwx
-        direct = wbase.is_leaf and wbase.grad is not None and wbase.grad.is_contiguous() and wbase.dim() == 4 and \
-            pwx.shape == (O1, 3) and pwx.storage_offset() == wbase.storage_offset()
-        if direct:
-            dwx, dst, ld, acc = None, wbase.grad, wbase.shape[1], 1
-        else:
-            dwx = torch.empty(O1, 3, dtype=_f32, device=dU.device)
-            dst, ld, acc = dwx, 3, 0
+        sink = _wx_sink(pwx, O1)                            # accumulated into the xyz columns of the first conv's gradient buffer, or ...
+        dwx = torch.empty(O1, 3, dtype=_f32, device=dU.device) if sink is None else None
+        dst = dwx if sink is None else sink
         err = L().cmf_setconv_dwx(O1, 1.0 / M, int(st1.training), _p(sums5), _p(fwd_sums), _p(st1.a), _p(st1.mean),
-                                  _p(st1.invstd), _p(dst), ld, acc, _lib.stream_ptr())
+                                  _p(st1.invstd), _p(dst), dst.shape[1], int(sink is not None), _lib.stream_ptr())
         _lib.check(err, "cmf_setconv_dwx")
         dy = None
         if ctx.needs_input_grad[1]:
@@ -831,89 +857,60 @@ class SetConvFn(Function):
                 g["b3"], g["w4"], g["g4"], g["b4"], g["w5"], g["g5"], g["b5"], g["w6"], g["g6"], g["b6"])
 
 
-def _block_forward(xyz_t, y, radius, nsample, bns, training, params, out=None, inference=False):
-    """Fill a cmf_setconv_desc, allocate saved/scratch/out on the CURRENT stream and issue
-    cmf_setconv_forward there.  out: optional (B*N, 64) strided view to write into."""
-    import ctypes
+_SC_W = [(j, 3 + 3 * j) for j in range(5)]          # cmf_setconv_desc.dw[j]: layer weights 2..6 at params[3, 6, 9, 12, 15]
+_SC_BN = [(l, 1 + 3 * l) for l in range(6)]         # .dgamma[l] / .dbeta[l]: BN layer l at params[1 + 3l] / params[2 + 3l]
+
+
+def _fill_setconv_desc(d, params, bns, B, N, S, O1, radius, training, ldy, defer_running_stats=False):
+    """The call-invariant part of a cmf_setconv_desc: geometry, hyper-parameters and the weight / BN / running-statistics
+    pointers of one PointLocalFeature (params, bns as set_conv_params gives them)."""
+    wx, ws = params[0], [params[k] for _, k in _SC_W]
+    assert all(w.is_contiguous() for w in ws) and wx.shape == (O1, 3) and wx.stride(1) == 1
+    d.B, d.N, d.S, d.O1, d.radius, d.training, d.ldy = B, N, S, O1, radius, int(training), ldy
+    for j, w in enumerate(ws):
+        d.C[j], d.w[j] = w.shape[0], w.data_ptr()
+    for l, bn in enumerate(bns):
+        _fill_bn(d, l, bn, training, defer_running_stats)
+    d.wx, d.ldwx = wx.data_ptr(), wx.stride(0)
+
+
+def _route_setconv_grads(d, params, dst, acc=True):
+    """_route_grads for the 18 parameters of a set-conv block.  The wx gradient goes to an (O1, 3) tensor or to the xyz columns of a
+    tensor shaped like the first conv's weight (its gradient buffer, or the second cloud's temporary): row stride = its shape[1]."""
+    fresh, out = _route_grads(d, params, dst, acc, _SC_W, _SC_BN)
+    d.dwx, d.lddwx, d.acc_wx = out[0].data_ptr(), out[0].shape[1], int(acc and fresh[0] is None)
+    return fresh
+
+
+def _block_forward(xyz_t, y, radius, nsample, bns, training, params, inference=False):
+    """Fill a cmf_setconv_desc, allocate saved/scratch/out on the CURRENT stream and issue cmf_setconv_forward there."""
     B, N, _ = xyz_t.shape
     dev = xyz_t.device
-    wx = params[0]
-    ws = [params[i].contiguous() for i in (3, 6, 9, 12, 15)]
     assert y.stride(2) == 1 and y.stride(0) == N * y.stride(1)
     xyz_t = xyz_t.contiguous()
     d = _lib.SetConvDesc()
-    d.B, d.N, d.S, d.O1, d.radius, d.training = B, N, nsample, y.shape[2], radius, int(training)
+    _fill_setconv_desc(d, params, bns, B, N, nsample, y.shape[2], radius, training, y.stride(1))
     d.inference = int(bool(inference) and not training)     # no backward call will follow: nothing is kept for one
-    for i, w in enumerate(ws):
-        d.C[i] = w.shape[0]
-        d.w[i] = w.data_ptr()
-    for l, bn in enumerate(bns):
-        d.eps[l] = bn.eps
-        d.momentum[l] = bn.momentum if bn.momentum is not None else 0.1
-        assert bn.momentum is not None, "cumulative moving average BN is not supported by the block call"
-        d.gamma[l], d.beta[l] = bn.weight.data_ptr(), bn.bias.data_ptr()
-        d.rmean[l], d.rvar[l] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        d.nbt[l] = bn.num_batches_tracked.data_ptr() if (training and bn.track_running_stats) else None
-    d.xyz, d.y, d.ldy = xyz_t.data_ptr(), y.data_ptr(), y.stride(1)
-    if wx.stride(1) != 1:
-        wx = wx.contiguous()
-    d.wx, d.ldwx = wx.data_ptr(), wx.stride(0)
-    n_saved, n_f, n_b = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
-    _lib.check(L().cmf_setconv_sizes(ctypes.addressof(d), ctypes.addressof(n_saved), ctypes.addressof(n_f),
-                                     ctypes.addressof(n_b)), "cmf_setconv_sizes")
-    saved = torch.empty(n_saved.value, dtype=_f32, device=dev)
-    scratch = torch.empty(n_f.value, dtype=_f32, device=dev)
-    if out is None:
-        out = torch.empty(B * N, ws[4].shape[0], dtype=_f32, device=dev)
+    n_saved, n_fwd, n_bwd, _ = _sizes("cmf_setconv_sizes", d, 4)    # n_bwd: the size valid for a backward call with or without d.dy
+    saved = torch.empty(n_saved, dtype=_f32, device=dev)
+    scratch = torch.empty(n_fwd, dtype=_f32, device=dev)
+    out = torch.empty(B * N, d.C[4], dtype=_f32, device=dev)
+    d.xyz, d.y = xyz_t.data_ptr(), y.data_ptr()
     d.saved, d.scratch, d.out, d.ldo = saved.data_ptr(), scratch.data_ptr(), out.data_ptr(), out.stride(0)
     _lib.check(L().cmf_setconv_forward(ctypes.addressof(d), _lib.stream_ptr()), "cmf_setconv_forward")
-    return out, dict(desc=d, keep=(xyz_t, y, wx, ws, saved), n_bwd=n_b.value, params=params)
+    return out, dict(desc=d, keep=(xyz_t, y, saved), n_bwd=n_bwd, params=params)
 
 
 def _block_backward(state, dout, need_dy):
     """cmf_setconv_backward on the CURRENT stream.  dout: (B*N, 64) view (unit channel stride).
     -> (dy or None, 18 parameter gradients; None where the kernel accumulated into a grad sink)."""
-    import ctypes
-    d, (xyz_t, y, wx, ws, saved), params = state["desc"], state["keep"], state["params"]
-    dev = dout.device
-    B, N, O1 = d.B, d.N, d.O1
-    if dout.stride(1) != 1 or dout.stride(0) % 4:
-        dout = dout.contiguous()
-    scratch = torch.empty(state["n_bwd"], dtype=_f32, device=dev)
+    d, params = state["desc"], state["params"]
+    dout = _row_major4(dout)
+    scratch = torch.empty(state["n_bwd"], dtype=_f32, device=dout.device)
     d.scratch, d.dout, d.lddout = scratch.data_ptr(), dout.data_ptr(), dout.stride(0)
-    grads = [None] * 18
-    # wx: the [:, :3] slice of the first conv's weight
-    pwx = params[0]
-    wbase = pwx._base if pwx._base is not None else pwx
-    if wbase.is_leaf and wbase.grad is not None and wbase.grad.is_contiguous() and wbase.dim() == 4 and \
-            pwx.shape == (O1, 3) and pwx.storage_offset() == wbase.storage_offset():
-        d.dwx, d.lddwx, d.acc_wx = wbase.grad.data_ptr(), wbase.shape[1], 1
-    else:
-        g = torch.empty(O1, 3, dtype=_f32, device=dev)
-        grads[0] = g
-        d.dwx, d.lddwx, d.acc_wx = g.data_ptr(), 3, 0
-    for i in range(5):                                   # layer weights 2..6 at params[3,6,9,12,15]
-        sink = grad_sink(params[3 + 3 * i])
-        if sink is not None:
-            d.dw[i], d.acc_w[i] = sink.data_ptr(), 1
-        else:
-            g = torch.empty_like(ws[i])
-            grads[3 + 3 * i] = g
-            d.dw[i], d.acc_w[i] = g.data_ptr(), 0
-    for l in range(6):                                   # (gamma, beta) of BN layer l at params[1+3l], params[2+3l]
-        sg, sb = grad_sink(params[1 + 3 * l]), grad_sink(params[2 + 3 * l])
-        if sg is not None and sb is not None:
-            d.dgamma[l], d.dbeta[l], d.acc_bn[l] = sg.data_ptr(), sb.data_ptr(), 1
-        else:
-            gg, gb = torch.empty_like(params[1 + 3 * l]), torch.empty_like(params[2 + 3 * l])
-            grads[1 + 3 * l], grads[2 + 3 * l] = gg, gb
-            d.dgamma[l], d.dbeta[l], d.acc_bn[l] = gg.data_ptr(), gb.data_ptr(), 0
-    dy = None
-    if need_dy:
-        dy = torch.empty(B, N, O1, dtype=_f32, device=dev)
-        d.dy = dy.data_ptr()
-    else:
-        d.dy = None
+    grads = _route_setconv_grads(d, params, _param_sinks(params, _SC_BN, d.O1))
+    dy = torch.empty(d.B, d.N, d.O1, dtype=_f32, device=dout.device) if need_dy else None
+    d.dy = _p(dy)
     _lib.check(L().cmf_setconv_backward(ctypes.addressof(d), _lib.stream_ptr()), "cmf_setconv_backward")
     return dy, grads
 
@@ -935,14 +932,19 @@ class SetConvBlockFn(Function):
         return (None, dy, None, None, None, None, *grads)
 
 
-import os as _os
+def _offsets(sizes):
+    """Float offsets of consecutive arenas, each kept 256-byte aligned; the last entry is the total."""
+    off = [0]
+    for v in sizes:
+        off.append(off[-1] + (v + 63) // 64 * 64)
+    return off
 
 
 class EncoderPlan:
     """Everything about a MultiScaleEncoder call that does not change from step to step, built once per
     (batch, points, training, device): the four cmf_setconv_desc structs with geometry, hyper-parameters and the
     parameter / BN-buffer pointers filled in (optimizers update parameters in place), and the arena sizes.  A call
-    then only sets the per-call pointers (xyz, y, saved, scratch, out) -- the Python work per encoder call drops
+    then only sets the per-call pointers (bind_forward / bind_backward) -- the Python work per encoder call drops
     from ~0.5 ms to a few tens of microseconds, which at N = 256 is what the GPU was waiting for."""
 
     def __init__(self, modules, B, N, O1, training, device, clouds=1):
@@ -950,51 +952,31 @@ class EncoderPlan:
         first call, [ns, 2 ns) the second.  Their BN running-statistics updates are deferred (cmf_bn_running_update,
         in call order) and the second call writes its parameter gradients to scratch tensors that are added to the
         sinks afterwards (two kernels accumulating into one buffer from different streams would race)."""
-        import ctypes
         ns = len(modules)
-        self.ns, self.clouds = ns, clouds
+        self.ns, self.clouds, self.o1 = ns, clouds, O1
         self.n = n = ns * clouds
         self.key = (B, N, O1, bool(training), str(device), clouds)
         self.descs = (_lib.SetConvDesc * n)()
-        self.keep, self.params, self.bns = [], [], []
-        self.n_saved, self.n_fwd, self.n_bwd, self.n_bwd_dy = [], [], [], []
+        self.params, self.bns = [], []
         defer = clouds > 1 and training
+        sizes = []
         for i in range(n):
             m = modules[i % ns]
             params, bns = set_conv_params(m)
-            d = self.descs[i]
-            wx = params[0]
-            ws = [params[j] for j in (3, 6, 9, 12, 15)]
-            assert all(w.is_contiguous() for w in ws) and wx.stride(1) == 1
-            d.B, d.N, d.S, d.O1, d.radius, d.training = B, N, m.nsample, O1, m.radius, int(training)
-            for j, w in enumerate(ws):
-                d.C[j] = w.shape[0]
-                d.w[j] = w.data_ptr()
-            for l, bn in enumerate(bns):
-                assert bn.momentum is not None, "cumulative moving average BN is not supported by the block call"
-                d.eps[l], d.momentum[l] = bn.eps, bn.momentum
-                d.gamma[l], d.beta[l] = bn.weight.data_ptr(), bn.bias.data_ptr()
-                d.rmean[l], d.rvar[l] = (None, None) if defer else (bn.running_mean.data_ptr(), bn.running_var.data_ptr())
-                d.nbt[l] = bn.num_batches_tracked.data_ptr() if (training and bn.track_running_stats and not defer) else None
-            d.wx, d.ldwx = wx.data_ptr(), wx.stride(0)
-            d.ldy = ns * O1                                         # y is a column slice of the stacked (B,N,ns*O1) GEMM output
-            c_s, c_f, c_b, c_bd = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
-            _lib.check(L().cmf_setconv_sizes(ctypes.addressof(d), ctypes.addressof(c_s), ctypes.addressof(c_f),
-                                             ctypes.addressof(c_b)), "cmf_setconv_sizes")
-            # the backward scratch is sized by path (cmflow_hip.h cmf_setconv_sizes): with an input gradient to produce (d.dy set) the
-            # second encoder's blocks sum the first layer's data gradient inside the GEMM and need no M x O1 slot for it
-            d.dy = 8                                                # (any non-null value: never dereferenced by the sizes call)
-            _lib.check(L().cmf_setconv_sizes(ctypes.addressof(d), None, None, ctypes.addressof(c_bd)), "cmf_setconv_sizes")
-            d.dy = None
-            self.n_saved.append(c_s.value); self.n_fwd.append(c_f.value); self.n_bwd.append(c_b.value); self.n_bwd_dy.append(c_bd.value)
+            # (ldy: y is a column slice of the stacked (B,N,ns*O1) GEMM output)
+            _fill_setconv_desc(self.descs[i], params, bns, B, N, m.nsample, O1, m.radius, training, ns * O1, defer)
+            sizes.append(_sizes("cmf_setconv_sizes", self.descs[i], 4))
             self.params.append(params); self.bns.append(bns)
+        # the backward scratch is sized by path (cmflow_hip.h cmf_setconv_sizes): with an input gradient to produce the second encoder's
+        # blocks sum the first layer's data gradient inside the GEMM and need no M x O1 slot for it (off_bwd_dy)
+        self.off_saved, self.off_fwd, self.off_bwd, self.off_bwd_dy = (_offsets(v) for v in zip(*sizes))
+        self.saved_per_cloud = self.off_saved[ns]                   # floats: the second call's arena starts here
         self.co = self.params[0][15].shape[0]
         self.modules = list(modules)
         self.update_table, self.temps = None, None
         if defer:                                                   # one table entry per (scale, BN layer)
             entries = (_lib.BnUpdateEntry * (ns * 6))()
             offs = (ctypes.c_longlong * 6)()
-            base = 0
             for i in range(ns):
                 _lib.check(L().cmf_setconv_bn_offsets(ctypes.addressof(self.descs[i]), ctypes.addressof(offs)), "cmf_setconv_bn_offsets")
                 for l, bn in enumerate(self.bns[i]):
@@ -1003,8 +985,7 @@ class EncoderPlan:
                     e.nbt = bn.num_batches_tracked.data_ptr() if bn.track_running_stats else None
                     e.C, e.momentum, e.eps = bn.num_features, bn.momentum, bn.eps
                     e.count = float(B * N * (modules[i].nsample if l < 3 else 1))
-                    e.offset = base + offs[l]
-                base += (self.n_saved[i] + 63) // 64 * 64          # same rounding as off_saved below
+                    e.offset = self.off_saved[i] + offs[l]
             raw = bytes(entries)
             self.update_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
             self.n_update = ns * 6
@@ -1013,18 +994,7 @@ class EncoderPlan:
             self.temps = [[torch.zeros_like(t._base) if j == 0 else torch.empty_like(t) for j, t in enumerate(p)]
                           for p in self.params[:ns]]
         self.check_ptrs = self._live_ptrs()
-        al = lambda v: (v + 63) // 64 * 64                          # keep every arena 256-byte aligned
-        self.off_saved = [0]
-        for v in self.n_saved:
-            self.off_saved.append(self.off_saved[-1] + al(v))
-        self.off_fwd, self.off_bwd, self.off_bwd_dy = [0], [0], [0]
-        for v in self.n_fwd:
-            self.off_fwd.append(self.off_fwd[-1] + al(v))
-        for v in self.n_bwd:
-            self.off_bwd.append(self.off_bwd[-1] + al(v))
-        for v in self.n_bwd_dy:
-            self.off_bwd_dy.append(self.off_bwd_dy[-1] + al(v))
-        self.saved_per_cloud = self.off_saved[ns]                   # floats: the second call's arena starts here
+        self._sink_probe = None
 
     def _live_ptrs(self):
         """Storage of EVERY tensor the descriptors point at, as the MODULES hold them now (the views kept in self.params
@@ -1056,47 +1026,63 @@ class EncoderPlan:
                     self._sink_probe = None
                     return False
                 probe.append(g.data_ptr())
-        if getattr(self, "_sink_probe", None) == probe:
+        if self._sink_probe == probe:
             return True
+        self._sink_probe = None
         self.sink_list, self.temp_list = [], []
         for i, (d, params) in enumerate(zip(self.descs, self.params)):
-            wsink = self._wx_sink(params[0])
-            sinks = [grad_sink(t) for t in params[1:]]
-            if wsink is None or any(x is None for x in sinks):
-                self._sink_probe = None
+            sinks = _param_sinks(params, _SC_BN, self.o1)
+            if any(x is None for x in sinks):
                 return False
-            acc = 1
-            if i >= self.ns:                                        # second call: write to scratch, added to the sinks afterwards
-                tmp = self.temps[i - self.ns]
-                self.sink_list += [wsink] + sinks
-                self.temp_list += tmp
-                wsink, sinks, acc = tmp[0], tmp[1:], 0
-            d.dwx, d.lddwx, d.acc_wx = wsink.data_ptr(), params[0].stride(0), acc
-            for j in range(5):
-                d.dw[j], d.acc_w[j] = sinks[2 + 3 * j].data_ptr(), acc
-            for l in range(6):
-                d.dgamma[l], d.dbeta[l], d.acc_bn[l] = sinks[3 * l].data_ptr(), sinks[3 * l + 1].data_ptr(), acc
+            if i < self.ns:
+                _route_setconv_grads(d, params, sinks)
+            else:                                                   # second call: write to scratch, added to the sinks afterwards
+                self.sink_list += sinks
+                self.temp_list += self.temps[i - self.ns]
+                _route_setconv_grads(d, params, self.temps[i - self.ns], acc=False)
         self._sink_probe = probe
         return True
 
-    @staticmethod
-    def _wx_sink(pwx):
-        base = pwx._base if pwx._base is not None else pwx
-        if base.is_leaf and base.grad is not None and base.grad.is_contiguous() and base.dim() == 4 and \
-                pwx.shape[1] == 3 and pwx.storage_offset() == base.storage_offset():
-            return base.grad
-        return None
+    def route_grads_per_call(self):
+        """Without sinks for everything: each gradient goes to its sink where it has one, else to a fresh tensor.
+        -> the n x 18 gradients autograd must be handed."""
+        self._sink_probe = None                                     # the descriptors no longer hold what sinks_ready() wrote
+        return [g for d, params in zip(self.descs, self.params)
+                for g in _route_setconv_grads(d, params, _param_sinks(params, _SC_BN, self.o1))]
+
+    def bind_forward(self, clouds, saved, scratch, outs, inference=0):
+        """The per-call pointers of a forward call.  clouds: (xyz (B,N,3), y_all (B,N,ns*O1)) per cloud, outs: (B*N, ns*co) per cloud;
+        block i = scale i % ns of cloud i // ns reads / writes its column slice of y_all / out."""
+        ns, o1, co = self.ns, self.o1, self.co
+        p_saved, p_scratch = saved.data_ptr(), scratch.data_ptr()
+        for i, d in enumerate(self.descs):
+            c, s = divmod(i, ns)
+            d.xyz, d.y = clouds[c][0].data_ptr(), clouds[c][1].data_ptr() + 4 * s * o1
+            d.saved, d.scratch = p_saved + 4 * self.off_saved[i], p_scratch + 4 * self.off_fwd[i]
+            d.out, d.ldo = outs[c].data_ptr() + 4 * s * co, ns * co
+            d.inference = inference
+
+    def bind_backward(self, clouds, saved, scratch, off_bwd, douts, dys):
+        """The per-call pointers of a backward call.  off_bwd: the offset table `scratch` was sized with (off_bwd: any call;
+        off_bwd_dy: every block produces its input gradient); douts: (B*N, ns*co) per cloud; dys: (B,N,ns*O1) or None per cloud."""
+        ns, o1, co = self.ns, self.o1, self.co
+        p_saved, p_scratch = saved.data_ptr(), scratch.data_ptr()
+        for i, d in enumerate(self.descs):
+            c, s = divmod(i, ns)
+            d.xyz, d.y = clouds[c][0].data_ptr(), clouds[c][1].data_ptr() + 4 * s * o1
+            d.saved, d.scratch = p_saved + 4 * self.off_saved[i], p_scratch + 4 * off_bwd[i]
+            d.dout, d.lddout = douts[c].data_ptr() + 4 * s * co, douts[c].stride(0)
+            d.dy, d.lddy = (dys[c].data_ptr() + 4 * s * o1, ns * o1) if dys[c] is not None else (None, 0)
 
 
-def _multi_call(backward, n, plan, sp, streams, main, counts=None):
-    """Issue the n chains of a plan on their streams, forked from and joined back into `main` with torch stream waits around
+def _multi_call(backward, plan, streams, main, counts=None):
+    """Issue the chains of a plan on their streams, forked from and joined back into `main` with torch stream waits around
     cmf_setconv_*_multi.  counts (forward, inference): (B,) int32 point counts of ragged samples -- the ball queries of all blocks are
     then the counted nested query (cmf_setconv_queries_counted), whatever NESTED_QUERIES says: a block's own query is not counted."""
-    import ctypes
     # The per-point tails of the n blocks (three <= 64-channel layers over the B*N points: latency, not work) run as batched
     # launches on the caller's stream -- behind the joined chains in forward, in front of the fork in backward; the chains on
     # the side streams carry the neighbourhood layers only (cmflow_hip.h, cmf_setconv_tail_*).
-    descs = ctypes.addressof(plan.descs)
+    n, descs = plan.n, ctypes.addressof(plan.descs)
     if backward:
         _lib.check(L().cmf_setconv_tail_backward(n, descs, main.cuda_stream), "cmf_setconv_tail_backward")
         stress_point([main])                    # (tests) between the tails and the bodies that consume their gradients
@@ -1130,6 +1116,7 @@ def _multi_call(backward, n, plan, sp, streams, main, counts=None):
         _lib.check(L().cmf_setconv_backward_bodies_multi(n, descs, ctypes.addressof(mp)), "cmf_setconv_backward_bodies_multi")
         stress_point([main])
         return
+    sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
     for st in streams:
         st.wait_stream(main)
     stress_point(streams)
@@ -1142,28 +1129,21 @@ def _multi_call(backward, n, plan, sp, streams, main, counts=None):
         _lib.check(L().cmf_setconv_tail_forward(n, descs, main.cuda_stream), "cmf_setconv_tail_forward")
 
 
-# Debug tap for tests: when a list, every multi-scale / dual-cloud forward call appends, per block, the ball-query indices the LIBRARY
-# issued (cmf_setconv_forward's first kernel; they sit at the head of the block's `saved` arena as int32 (B, N, S)):
-# (radius, nsample, idx clone).  None (default): nothing is copied.
-IDX_TAP = None
-NESTED_QUERIES = os.environ.get("CMF_NESTED_QUERIES", "1") != "0"       # 0: every block issues its own ball query (A/B)
-
-
-def _tap_indices(plan, saved, blocks):
+def _tap_indices(plan, saved):
     if IDX_TAP is None:
         return
-    for i in blocks:
-        d = plan.descs[i]
+    for i, d in enumerate(plan.descs):
         m = d.B * d.N * d.S
         idx = saved[plan.off_saved[i]:plan.off_saved[i] + m].view(torch.int32).view(d.B, d.N, d.S)
         IDX_TAP.append((float(d.radius), int(d.S), idx.clone()))
 
 
 class MultiScaleBlockFn(Function):
-    """The four set-conv scales of a MultiScaleEncoder (radarflow_util.py:101-118) as one autograd node and ONE
-    C-ABI call per direction (cmf_setconv_forward_multi / _backward_multi: each scale is issued on its own HIP
-    stream from its own host thread inside the library -- with N = 256 the ~20 / ~45 kernels of a scale run about
-    as long as they take to enqueue, so one host thread cannot keep four streams fed).  The scales write disjoint
+    """The four set-conv scales of a MultiScaleEncoder (radarflow_util.py:101-118) as one autograd node and a few C-ABI
+    calls per direction (_multi_call: cmf_setconv_forward_heads_multi + cmf_setconv_tail_forward, cmf_setconv_tail_backward +
+    cmf_setconv_backward_bodies_multi; each scale's chain is issued on its own HIP stream from its own host thread inside the
+    library -- with N = 256 the ~20 / ~45 kernels of a scale run about as long as they take to enqueue, so one host thread
+    cannot keep four streams fed -- and the per-point tails of all scales as batched launches).  The scales write disjoint
     channel slices of one (B,N,4*64) output and the input gradient comes back as one (B,N,4*O1) tensor, so the
     concat / slice-gradient kernels are gone too.  With every parameter gradient accumulated in place (grad sinks)
     the parameters are not even autograd inputs of the node.  Numerics: same kernels per scale as SetConvBlockFn."""
@@ -1173,85 +1153,38 @@ class MultiScaleBlockFn(Function):
         """counts: None, or (inference only) the (B,) int32 point counts of RAGGED samples on the device -- xyz_t / y_all are then padded
         to N rows per sample and the blocks run behind the counted nested ball query (_multi_call): neighbours of a valid point are
         points of its own sample below its count, a padded point's neighbour is point 0 of its sample."""
-        import ctypes
         B, N, _ = xyz_t.shape
         n, co, dev = plan.n, plan.co, xyz_t.device
         xyz_t = xyz_t.contiguous()
-        assert y_all.is_contiguous() and y_all.shape[2] == n * plan.descs[0].O1
-        main = torch.cuda.current_stream()
+        assert y_all.is_contiguous() and y_all.shape[2] == n * plan.o1
         out_all = torch.empty(B * N, n * co, dtype=_f32, device=dev)
         saved = torch.empty(plan.off_saved[-1], dtype=_f32, device=dev)
         scratch = torch.empty(plan.off_fwd[-1], dtype=_f32, device=dev)
-        o1 = plan.descs[0].O1
         inference = int(not any(ctx.needs_input_grad) and not plan.descs[0].training)   # no backward call will follow
-        for i in range(n):
-            d = plan.descs[i]
-            d.xyz, d.y = xyz_t.data_ptr(), y_all.data_ptr() + 4 * i * o1
-            d.saved, d.scratch = saved.data_ptr() + 4 * plan.off_saved[i], scratch.data_ptr() + 4 * plan.off_fwd[i]
-            d.out, d.ldo = out_all.data_ptr() + 4 * i * co, n * co
-            d.inference = inference
-        sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
-        _multi_call(False, n, plan, sp, streams, main, counts=counts)
-        _tap_indices(plan, saved, range(n))
+        plan.bind_forward([(xyz_t, y_all)], saved, scratch, [out_all], inference)
+        _multi_call(False, plan, streams, torch.cuda.current_stream(), counts=counts)
+        _tap_indices(plan, saved)
         ctx.plan, ctx.keep, ctx.streams, ctx.sink_mode = plan, (xyz_t, y_all, saved), streams, sink_mode
         return out_all.view(B, N, n * co)
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         plan, (xyz_t, y_all, saved), streams = ctx.plan, ctx.keep, ctx.streams
-        n, co = plan.n, plan.co
-        B, N, o1 = plan.descs[0].B, plan.descs[0].N, plan.descs[0].O1
-        dev = dout.device
-        dout = dout.reshape(B * N, n * co)
-        if dout.stride(1) != 1 or dout.stride(0) % 4:
-            dout = dout.contiguous()
-        main = torch.cuda.current_stream()
+        d0 = plan.descs[0]
+        dout = _row_major4(dout.reshape(d0.B * d0.N, plan.n * plan.co))
         need_dy = ctx.needs_input_grad[1]
         off_bwd = plan.off_bwd_dy if need_dy else plan.off_bwd
-        scratch = torch.empty(off_bwd[-1], dtype=_f32, device=dev)
-        dy_all = torch.empty(B, N, n * o1, dtype=_f32, device=dev) if need_dy else None
-        grads = []
-        if ctx.sink_mode and not plan.sinks_ready():
+        scratch = torch.empty(off_bwd[-1], dtype=_f32, device=dout.device)
+        dy_all = torch.empty(d0.B, d0.N, plan.n * plan.o1, dtype=_f32, device=dout.device) if need_dy else None
+        if not ctx.sink_mode:
+            grads = plan.route_grads_per_call()
+        elif plan.sinks_ready():                                    # the sink pointers sit in the descriptors
+            grads = ()
+        else:
             raise RuntimeError("parameter .grad buffers disappeared between forward and backward")
-        for i in range(n):
-            d, params = plan.descs[i], plan.params[i]
-            d.xyz, d.y = xyz_t.data_ptr(), y_all.data_ptr() + 4 * i * o1
-            d.saved, d.scratch = saved.data_ptr() + 4 * plan.off_saved[i], scratch.data_ptr() + 4 * off_bwd[i]
-            d.dout, d.lddout = dout.data_ptr() + 4 * i * co, dout.stride(0)
-            d.dy, d.lddy = (dy_all.data_ptr() + 4 * i * o1, n * o1) if need_dy else (None, 0)
-            if ctx.sink_mode:                                       # sink pointers already sit in the descriptors
-                continue
-            plan._sink_probe = None                                 # the descriptors get per-call gradient buffers below
-            g = [None] * 18
-            wsink = plan._wx_sink(params[0])
-            if wsink is not None:
-                d.dwx, d.lddwx, d.acc_wx = wsink.data_ptr(), params[0].stride(0), 1
-            else:
-                if ctx.sink_mode:
-                    raise RuntimeError("parameter .grad buffers disappeared between forward and backward")
-                g[0] = torch.empty(o1, 3, dtype=_f32, device=dev)
-                d.dwx, d.lddwx, d.acc_wx = g[0].data_ptr(), 3, 0
-            for j in range(5):
-                sink = grad_sink(params[3 + 3 * j])
-                if sink is not None:
-                    d.dw[j], d.acc_w[j] = sink.data_ptr(), 1
-                else:
-                    g[3 + 3 * j] = torch.empty_like(params[3 + 3 * j])
-                    d.dw[j], d.acc_w[j] = g[3 + 3 * j].data_ptr(), 0
-            for l in range(6):
-                sg, sb = grad_sink(params[1 + 3 * l]), grad_sink(params[2 + 3 * l])
-                if sg is not None and sb is not None:
-                    d.dgamma[l], d.dbeta[l], d.acc_bn[l] = sg.data_ptr(), sb.data_ptr(), 1
-                else:
-                    g[1 + 3 * l], g[2 + 3 * l] = torch.empty_like(params[1 + 3 * l]), torch.empty_like(params[2 + 3 * l])
-                    d.dgamma[l], d.dbeta[l], d.acc_bn[l] = g[1 + 3 * l].data_ptr(), g[2 + 3 * l].data_ptr(), 0
-            grads += g
-        if ctx.sink_mode and any(t is not None for t in grads):
-            raise RuntimeError("parameter .grad buffers disappeared between forward and backward")
-        sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
-        _multi_call(True, n, plan, sp, streams, main)
-        return (None, dy_all, None, None, None, None, *(() if ctx.sink_mode else grads))
+        plan.bind_backward([(xyz_t, y_all)], saved, scratch, off_bwd, [dout], [dy_all])
+        _multi_call(True, plan, streams, torch.cuda.current_stream())
+        return (None, dy_all, None, None, None, None, *grads)
 
 
 class DualCloudBlockFn(Function):
@@ -1264,61 +1197,47 @@ class DualCloudBlockFn(Function):
 
     @staticmethod
     def forward(ctx, xyz1, y1, xyz2, y2, plan, streams):
-        import ctypes
         B, N, _ = xyz1.shape
-        n, ns, co, dev = plan.n, plan.ns, plan.co, xyz1.device
-        xyz = (xyz1.contiguous(), xyz2.contiguous())
-        ys = (y1, y2)
-        o1 = plan.descs[0].O1
-        assert y1.is_contiguous() and y2.is_contiguous() and y1.shape[2] == ns * o1
-        main = torch.cuda.current_stream()
+        ns, co, dev = plan.ns, plan.co, xyz1.device
+        clouds = [(xyz1.contiguous(), y1), (xyz2.contiguous(), y2)]
+        assert y1.is_contiguous() and y2.is_contiguous() and y1.shape[2] == ns * plan.o1
         outs = [torch.empty(B * N, ns * co, dtype=_f32, device=dev) for _ in range(2)]
         saved = torch.empty(2 * plan.saved_per_cloud, dtype=_f32, device=dev)
         scratch = torch.empty(plan.off_fwd[-1], dtype=_f32, device=dev)
-        for i in range(n):
-            c, sc = divmod(i, ns)
-            d = plan.descs[i]
-            d.xyz, d.y = xyz[c].data_ptr(), ys[c].data_ptr() + 4 * sc * o1
-            d.saved, d.scratch = saved.data_ptr() + 4 * plan.off_saved[i], scratch.data_ptr() + 4 * plan.off_fwd[i]
-            d.out, d.ldo = outs[c].data_ptr() + 4 * sc * co, ns * co
-        sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
-        _multi_call(False, n, plan, sp, streams, main)
-        _tap_indices(plan, saved, range(n))
+        plan.bind_forward(clouds, saved, scratch, outs)
+        _multi_call(False, plan, streams, torch.cuda.current_stream())
+        _tap_indices(plan, saved)
         if plan.update_table is not None:                           # running statistics: first call, then second call
             _lib.check(L().cmf_bn_running_update(plan.n_update, plan.update_table.data_ptr(), 2, saved.data_ptr(),
                                                  saved.data_ptr() + 4 * plan.saved_per_cloud, _lib.stream_ptr()),
                        "cmf_bn_running_update")
-        ctx.plan, ctx.keep, ctx.streams = plan, (xyz, ys, saved), streams
+        ctx.plan, ctx.keep, ctx.streams = plan, (clouds, saved), streams
         return outs[0].view(B, N, ns * co), outs[1].view(B, N, ns * co)
 
     @staticmethod
     def backward(ctx, dout1, dout2):
-        import ctypes
-        plan, (xyz, ys, saved), streams = ctx.plan, ctx.keep, ctx.streams
-        n, ns, co = plan.n, plan.ns, plan.co
-        B, N, o1 = plan.descs[0].B, plan.descs[0].N, plan.descs[0].O1
-        dev = dout1.device
-        douts = []
-        for g in (dout1, dout2):
-            g = g.reshape(B * N, ns * co)
-            douts.append(g if (g.stride(1) == 1 and g.stride(0) % 4 == 0) else g.contiguous())
+        plan, (clouds, saved), streams = ctx.plan, ctx.keep, ctx.streams
+        d0 = plan.descs[0]
+        douts = [_row_major4(g.reshape(d0.B * d0.N, plan.ns * plan.co)) for g in (dout1, dout2)]
         if not plan.sinks_ready():
             raise RuntimeError("parameter .grad buffers disappeared between forward and backward")
-        main = torch.cuda.current_stream()
-        scratch = torch.empty(plan.off_bwd[-1], dtype=_f32, device=dev)      # (sized without d.dy: never smaller than with it)
-        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[3])
-        dys = [torch.empty(B, N, ns * o1, dtype=_f32, device=dev) if need[c] else None for c in range(2)]
-        for i in range(n):
-            c, sc = divmod(i, ns)
-            d = plan.descs[i]
-            d.xyz, d.y = xyz[c].data_ptr(), ys[c].data_ptr() + 4 * sc * o1
-            d.saved, d.scratch = saved.data_ptr() + 4 * plan.off_saved[i], scratch.data_ptr() + 4 * plan.off_bwd[i]
-            d.dout, d.lddout = douts[c].data_ptr() + 4 * sc * co, douts[c].stride(0)
-            d.dy, d.lddy = (dys[c].data_ptr() + 4 * sc * o1, ns * o1) if need[c] else (None, 0)
-        sp = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
-        _multi_call(True, n, plan, sp, streams, main)
+        scratch = torch.empty(plan.off_bwd[-1], dtype=_f32, device=dout1.device)     # (a cloud may need no input gradient: the any-call size)
+        dys = [torch.empty(d0.B, d0.N, plan.ns * plan.o1, dtype=_f32, device=dout1.device) if need else None
+               for need in (ctx.needs_input_grad[1], ctx.needs_input_grad[3])]
+        plan.bind_backward(clouds, saved, scratch, plan.off_bwd, douts, dys)
+        _multi_call(True, plan, streams, torch.cuda.current_stream())
         torch._foreach_add_(plan.sink_list, plan.temp_list)         # the second call's parameter gradients
         return None, dys[0], None, dys[1], None, None
+
+
+def _plan(encoder, modules, B, N, o1, training, device, clouds=1):
+    """The cached EncoderPlan of this call shape, rebuilt when a parameter or buffer of the modules was re-allocated."""
+    plans = encoder.__dict__.setdefault("_plans", {})
+    key = (B, N, o1, bool(training), str(device), clouds)
+    plan = plans.get(key)
+    if plan is None or not plan.valid():
+        plan = plans[key] = EncoderPlan(modules, B, N, o1, training, device, clouds=clouds)
+    return plan
 
 
 def dual_cloud_set_conv(encoder, modules, streams, xyz1, y1, xyz2, y2):
@@ -1326,22 +1245,17 @@ def dual_cloud_set_conv(encoder, modules, streams, xyz1, y1, xyz2, y2):
     gradient sinks, equal shapes) do not hold and the caller should issue the two calls one after the other."""
     if not torch.is_grad_enabled() or xyz1.shape != xyz2.shape or y1.shape != y2.shape:
         return None
-    B, N, _ = xyz1.shape
-    o1 = y1.shape[2] // len(modules)
-    training = modules[0].mlp_bns[0].training
-    if not training:
+    if not modules[0].mlp_bns[0].training:
         return None
-    key = (B, N, o1, True, str(xyz1.device), 2)
-    plans = encoder.__dict__.setdefault("_plans", {})
-    plan = plans.get(key)
-    if plan is None or not plan.valid():
-        plan = plans[key] = EncoderPlan(modules, B, N, o1, True, xyz1.device, clouds=2)
+    B, N, _ = xyz1.shape
+    plan = _plan(encoder, modules, B, N, y1.shape[2] // len(modules), True, xyz1.device, clouds=2)
     if not plan.sinks_ready():
         return None
     return DualCloudBlockFn.apply(xyz1, y1.contiguous(), xyz2, y2.contiguous(), plan, streams)
 
 
 def set_conv_params(module):
+    """The 18 parameters of a PointLocalFeature in block-call order (wx = the xyz columns of the first conv) and its six BN modules."""
     w2d = lambda conv: conv.weight.view(conv.weight.shape[0], conv.weight.shape[1])
     c, b = module.mlp_convs, module.mlp_bns
     c2, b2 = module.mlp2_convs, module.mlp2_bns
@@ -1355,18 +1269,13 @@ def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all, counts=None):
     counts ((B,) int32 on the device): RAGGED samples padded to N rows, inference only (eval-mode BatchNorm is row-wise; under
     torch.no_grad()), N <= 1024 (the counted one-scan ball query) -- refused otherwise rather than sent down an uncounted path."""
     B, N, _ = xyz_t.shape
-    o1 = y_all.shape[2] // len(modules)
     training = modules[0].mlp_bns[0].training
     if counts is not None:
         if training or torch.is_grad_enabled():
             raise RuntimeError("ragged set-conv blocks are inference only (eval-mode BatchNorm, torch.no_grad())")
         if N > 1024:
             raise ValueError("ragged batches cover clouds of up to 1024 points (the counted one-scan ball query); got Nmax = %d" % N)
-    key = (B, N, o1, bool(training), str(xyz_t.device), 1)
-    plans = encoder.__dict__.setdefault("_plans", {})
-    plan = plans.get(key)
-    if plan is None or not plan.valid():
-        plan = plans[key] = EncoderPlan(modules, B, N, o1, training, xyz_t.device)
+    plan = _plan(encoder, modules, B, N, y_all.shape[2] // len(modules), training, xyz_t.device)
     y_all = y_all.contiguous()
     sink_mode = torch.is_grad_enabled() and plan.sinks_ready()
     params = () if (sink_mode or not torch.is_grad_enabled()) else tuple(t for p in plan.params for t in p)
@@ -1378,17 +1287,9 @@ def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all, counts=None):
 
 def set_conv(module, xyz_t, y):
     """module: PointLocalFeature; y: (B,N,O1) view of the hoisted first-conv features."""
-    w2d = lambda conv: conv.weight.view(conv.weight.shape[0], conv.weight.shape[1])
-    c, b = module.mlp_convs, module.mlp_bns
-    c2, b2 = module.mlp2_convs, module.mlp2_bns
-    params = [w2d(c[0])[:, :3], b[0].weight, b[0].bias, w2d(c[1]), b[1].weight, b[1].bias, w2d(c[2]), b[2].weight, b[2].bias,
-              w2d(c2[0]), b2[0].weight, b2[0].bias, w2d(c2[1]), b2[1].weight, b2[1].bias, w2d(c2[2]), b2[2].weight, b2[2].bias]
-    bns = [b[0], b[1], b[2], b2[0], b2[1], b2[2]]
+    params, bns = set_conv_params(module)
     fn = SetConvBlockFn if USE_BLOCK_CALLS else SetConvFn
-    return fn.apply(xyz_t, y, module.radius, module.nsample, bns, b[0].training, *params)
-
-
-USE_BLOCK_CALLS = True
+    return fn.apply(xyz_t, y, module.radius, module.nsample, bns, bns[0].training, *params)
 
 
 # ---- cost volume (FeatureCorrelator) --------------------------------------------------------------

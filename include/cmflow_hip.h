@@ -435,13 +435,18 @@ typedef struct cmf_setconv_desc {
     int idx_ready;               /* 1: this block's ball query has been issued already (cmf_setconv_queries wrote the indices into
                                     `saved`); the forward call does not launch its own */
 } cmf_setconv_desc;
-/* Arena sizes in floats (each pointer may be NULL).  The arenas are sized by PATH: a block whose shapes take the gathering GEMMs
- * (M = B*N*S and O1, C[0] multiples of 128, ldy a multiple of 4: the second encoder) keeps M row indices + 3*O1 floats where the
- * materialised first-layer tensor would take M x O1, and -- in scratch_bwd, when d->dy is set at the time of the sizes call, i.e. the
- * backward call will produce an input gradient -- (B*N + M/64) x O1 + 6 M floats where the data gradient into that layer would
- * take M x O1.  scratch_bwd asked with d->dy == NULL is never smaller than with it set, so it is valid for either backward call.
+/* Arena sizes in floats (each pointer may be NULL); host arithmetic over the SHAPE fields of the descriptor (B, N, S, O1, C, ldy,
+ * training) -- no pointer of it is read.  The arenas are sized by PATH: a block whose shapes take the gathering GEMMs (M = B*N*S and
+ * O1, C[0] multiples of 128, ldy a multiple of 4: the second encoder) keeps M row indices + 3*O1 floats where the materialised
+ * first-layer tensor would take M x O1.
+ *   scratch_bwd             valid for ANY backward call on these shapes;
+ *   scratch_bwd_input_grad  valid only for a backward call that sets d->dy (produces the input gradient): such a block with S >= 2
+ *                           then holds (B*N + M/64) x O1 + 6 M floats where the data gradient into the first layer would take M x O1.
+ *                           Never larger than scratch_bwd, equal to it for every other block.  A backward call without d->dy on an
+ *                           arena of this size overruns it.
  * With the compact sizes d->y and d->w[0] must be 16-byte aligned (the forward / backward calls refuse them otherwise). */
-int cmf_setconv_sizes(const cmf_setconv_desc *d, long long *saved_floats, long long *scratch_fwd, long long *scratch_bwd);
+int cmf_setconv_sizes(const cmf_setconv_desc *d, long long *saved_floats, long long *scratch_fwd, long long *scratch_bwd,
+                      long long *scratch_bwd_input_grad);
 /* Device memory the library holds on the current device outside caller-provided arenas: the per-(stream, slot) scratch buffers of the
  * drop-in entry points (cmf_ball_query spill lists, cmf_group_points_grad plans / inverse indices), live + retired, in bytes. */
 long long cmf_mem_stats(void);
@@ -500,12 +505,10 @@ typedef struct cmf_bn_update_entry {
 int cmf_bn_running_update(int n_entries, const cmf_bn_update_entry *table, int n_calls, const float *saved0,
                           const float *saved1, void *stream);
 
-/* The independent scales of a MultiScaleEncoder (radarflow_util.py:101-118) in one call: descs[i] is issued on
- * streams[i] from its own host thread inside the library (n <= 16).  The caller orders the streams against its own
- * (events before and after); nothing is synchronised. */
-int cmf_setconv_forward_multi(int n, const cmf_setconv_desc *descs, void *const *streams);
-int cmf_setconv_backward_multi(int n, const cmf_setconv_desc *descs, void *const *streams);
-/* The same with the per-point tails (layers 4-6: three <= 64-channel layers over the B*N points) taken out of the chains and
+/* The independent scales of a MultiScaleEncoder (radarflow_util.py:101-118) in one call (the *_multi entry points below):
+ * descs[i] is issued on streams[i] from its own host thread inside the library (n <= 16).  The caller orders the streams
+ * against its own (events before and after); nothing is synchronised.
+ * The per-point tails (layers 4-6: three <= 64-channel layers over the B*N points) are taken out of the chains and
  * run for ALL blocks of the call as batched launches on one stream -- one launch per kernel of the tail instead of one per
  * block (at N = 256 these kernels are 128 workgroups of latency each; the eight chains of an encoder call spent 1.5 ms of
  * the 22 ms training step in them).  Forward: cmf_setconv_forward_heads_multi (up to the max over the ball, per stream),
@@ -602,7 +605,6 @@ typedef struct cmf_radar_loss_desc {
     float *d_pred_f, *d_pre_trans, *d_mseg_pre;                                /* (B,3,N), (B,4,4), (B,N) or NULL */
     float *workspace;                                                          /* cmf_radar_loss_workspace_nb floats */
 } cmf_radar_loss_desc;
-long long cmf_radar_loss_workspace(int b, int n);                  /* = cmf_radar_loss_workspace_nb(b, n, 8) */
 long long cmf_radar_loss_workspace_nb(int b, int n, int num_nb);   /* floats; num_nb as in the descriptor */
 int cmf_radar_loss(const cmf_radar_loss_desc *d, void *stream);
 int cmf_radar_loss_tiled(const cmf_radar_loss_desc *d, void *stream);   /* workspace: cmf_radar_loss_workspace_tiled */

@@ -101,3 +101,37 @@ def test_ctypes_structs_match_the_header(tmp_path):
     want = [ctypes.sizeof(_lib.SetConvDesc), _lib.SetConvDesc.acc_bn.offset, ctypes.sizeof(_lib.BnUpdateEntry),
             _lib.BnUpdateEntry.offset.offset, ctypes.sizeof(_lib.GemmLaunchRecord), ctypes.sizeof(_lib.MlpDesc), _lib.MlpDesc.acc_bn.offset]
     assert got == want
+
+
+def test_setconv_sizes_are_a_function_of_the_shape_fields_alone(so_path):
+    """cmf_setconv_sizes is host arithmetic over B, N, S, O1, C, ldy, training.  For the blocks of the model's two encoders (cmflow.py:
+    32/32/64 | 64/64/64 and 512/256/64 | 64/64/64, four scales: ldy = 4*O1): the any-call backward scratch is never smaller than the
+    one of a call that produces the input gradient, strictly larger exactly where the gathering layout sums that gradient inside the
+    GEMM (M = B*N*S, O1 and C[0] multiples of 128, ldy a multiple of 4, S >= 2), and no number depends on the output pointer d.dy."""
+    from cmflow_amd import _lib
+    lib = ctypes.CDLL(so_path)
+    encoders = [(32, (32, 64, 64, 64, 64)), (512, (256, 64, 64, 64, 64))]
+    cases = [(enc, B, 256, S) for enc in encoders for B in (1, 8) for S in (4, 8, 16, 32)]
+    cases += [(encoders[1], 1, N, S) for N, S in ((40, 16), (48, 16), (56, 16), (24, 32), (250, 4))]   # the guard-band test's blocks
+
+    def sizes(d):
+        out = [ctypes.c_longlong(-1) for _ in range(4)]
+        assert lib.cmf_setconv_sizes(ctypes.byref(d), *[ctypes.byref(v) for v in out]) == 0
+        return [v.value for v in out]
+
+    compact = 0
+    for (O1, C), B, N, S in cases:
+        d = _lib.SetConvDesc()
+        d.B, d.N, d.S, d.O1, d.ldy, d.training = B, N, S, O1, 4 * O1, 1
+        for i, c in enumerate(C):
+            d.C[i] = c
+        saved, fwd, bwd, bwd_dy = got = sizes(d)
+        assert min(got) > 0, (got, B, N, S, O1)
+        gathers = (B * N * S) % 128 == 0 and O1 % 128 == 0 and C[0] % 128 == 0 and d.ldy % 4 == 0 and S >= 2
+        assert (bwd > bwd_dy) if gathers else (bwd == bwd_dy), (got, B, N, S, O1)
+        compact += gathers
+        d.dy = 8                                             # (never dereferenced: no device, no allocation here)
+        assert sizes(d) == got, (B, N, S, O1)
+        only = ctypes.c_longlong(-1)                         # each out-pointer may be NULL
+        assert lib.cmf_setconv_sizes(ctypes.byref(d), None, None, None, ctypes.byref(only)) == 0 and only.value == bwd_dy
+    assert 0 < compact < len(cases)                          # both layouts are covered
