@@ -4,6 +4,7 @@
 #include <atomic>
 #include <mutex>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define CMF_WAVE 64
 
@@ -13,6 +14,14 @@
 static inline int cmf_launch_status() { return (int)hipGetLastError(); }
 
 static inline int cmf_divup(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The A/B switches of the host code: on unless the variable is set and starts with '0'.  Read once per switch:
+//   static const bool on = cmf_env_on("CMF_X");
+static inline bool cmf_env_on(const char *name)
+{
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is an attribute of (function, DEVICE): a process-wide `static bool` would
 // leave a second device without it (launch failure above 64 KB).  One bit per device, atomics (entry points are called from
@@ -117,3 +126,26 @@ int cmf_affine_relu_batch(int n, const CmfAffineArgs *a, hipStream_t st);       
 int cmf_splitk_reduce_batch(int n, const CmfSplitkArgs *a, hipStream_t st);              // gemm.hip
 int cmf_thin_fwd_batch(int n, const GemmArgs *g, hipStream_t st);                        // thin_gemm.hip: A[M,K] W[N,K]^T, K, N <= 64, same (N, K) for all
 int cmf_thin_bwd_layer_batch(int n, CmfThinBwdCall *c, hipStream_t st);                  // thin_gemm.hip: kernels only (no slab sum), same widths / mode
+
+// ---- internal entry points the block sequencer (setconv_block.hip) calls across files --------------------------------
+// setconv_chain.hip: the narrow block's neighbour-slot layers as register-chain passes with eval-mode BN; bn0 / bn1 / bn2 are whole
+// folded blocks (mean | invstd | a | c).  mode: 0 inference, 1 max over the ball + argmax + selected pre-activations, 2 / 3 backward
+// of layers 3 / 2
+bool cmf_setconv_chain_supported(int N, int S, int O1, int C2, int C3, long long M);
+long long cmf_setconv_chain_waves(long long M, int backward);
+int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
+                           long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
+                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *dU_in, float *dU_out,
+                           float *slabs, void *stream);
+int cmf_setconv_chain_infer(long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
+                            long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
+                            long long ldo, void *stream);
+// pointwise.hip: the max over the ball that also keeps the selected pre-activations, its backward per point, and cmf_colsum with
+// the first 2*C columns stored to dst0 / dst1
+int cmf_bn_relu_maxpool_sel(long long P, int S, int C, const float *z, const float *a, const float *c, float *out, long long ldo,
+                            unsigned char *argmax, float *zsel, void *stream);
+int cmf_maxpool_bwd_point_sel(long long P, int C, const float *dout, long long ldd, const float *zsel, const float *a, const float *c,
+                              const float *mean, const float *invstd, float *g, float *partial, void *stream);
+int cmf_colsum_store(int tiles, int ncols, const float *partial, float *out, int C, float *dst0, float *dst1, void *stream);
+void cmf_gemm_dx_gather_sum_hint(long long points);                                      // gemm.hip
+bool cmf_ball_query_multi_takes(int n, int nq, const int *nsamples);                     // neighbor.hip

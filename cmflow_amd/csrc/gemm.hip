@@ -1630,14 +1630,14 @@ static int gemm_diag_rt()
 // 256 x 128 tiles for tall interior shapes (env CMF_GEMM_TALL=0: the 128 x 128 tiles everywhere, A/B)
 static bool gemm_tall()
 {
-    static const bool on = !(getenv("CMF_GEMM_TALL") && getenv("CMF_GEMM_TALL")[0] == '0');
+    static const bool on = cmf_env_on("CMF_GEMM_TALL");
     return on;
 }
 
 // 128 x 256 tiles for the gathering forward GEMM (env CMF_GEMM_WIDE=0: 128 x 128, A/B)
 static bool gemm_wide()
 {
-    static const bool on = !(getenv("CMF_GEMM_WIDE") && getenv("CMF_GEMM_WIDE")[0] == '0');
+    static const bool on = cmf_env_on("CMF_GEMM_WIDE");
     return on;
 }
 

@@ -1384,7 +1384,7 @@ extern "C" int cmf_group_points_grad(int b, int c, int n, int npoints, int nsamp
     // per-centre lists of 16 / 32 / 64 slots: the pad-folded CSR gather -- deterministic, no atomics, and faster than the
     // LDS-atomic kernel (BASELINE config 5, C = 64 / 128: 859 / 1622 us against 1081 / 2148 us; the tiled deterministic
     // kernel: 1747 / 3330 us).  CMF_GROUP_GRAD_CSR=0 falls through to the older kernels (A/B).
-    static const bool use_csr = !(getenv("CMF_GROUP_GRAD_CSR") && getenv("CMF_GROUP_GRAD_CSR")[0] == '0');
+    static const bool use_csr = cmf_env_on("CMF_GROUP_GRAD_CSR");
     if (!balanced && use_csr && (nsample == 16 || nsample == 32 || nsample == 64) && n <= GC_MAX_N && total <= (1 << 30) &&
         (((uintptr_t)grad_out) & 15) == 0) {
         if (nsample == 64) return launch_csr<64>(b, c, n, (int)total, grad_out, idx, grad_points, st);
@@ -1427,7 +1427,7 @@ extern "C" int cmf_group_points_grad(int b, int c, int n, int npoints, int nsamp
     }
     // rows of the model's sizes: one plan kernel + the plan form of the balanced kernel (CMF_GROUP_GRAD_PLAN=0: the inverse
     // index + balanced kernel below, diagnostics)
-    static const bool use_plan = !(getenv("CMF_GROUP_GRAD_PLAN") && getenv("CMF_GROUP_GRAD_PLAN")[0] == '0');
+    static const bool use_plan = cmf_env_on("CMF_GROUP_GRAD_PLAN");
     if (use_plan && balanced && n <= GPL_MAX_N) {
         int ch_per_wg = GG_CH;
         while (ch_per_wg > 2 && (long long)b * cmf_divup(c, ch_per_wg) < 1024) ch_per_wg /= 2;

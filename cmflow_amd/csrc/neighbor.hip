@@ -671,7 +671,7 @@ static int ball_query_grid(int b, int n, int m, float radius, int nsample, const
 // positive finite number has no grid; the scan handles it like the reference.
 static bool ball_query_grid_takes(int n, float radius)
 {
-    static const bool use_grid = !(getenv("CMF_BALL_QUERY_GRID") && getenv("CMF_BALL_QUERY_GRID")[0] == '0');
+    static const bool use_grid = cmf_env_on("CMF_BALL_QUERY_GRID");
     return use_grid && n >= 4096 && n <= BQG_MAX_N && radius > 0.f && radius < 3.0e38f;
 }
 
@@ -695,7 +695,7 @@ int cmf_ball_query_defined(int b, int n, int m, float radius, int nsample, const
     CMF_CHECK_ARG(b >= 0 && n >= 0 && m >= 0 && nsample > 0);
     if (b == 0 || m == 0) return 0;
     CMF_CHECK_ARG(new_xyz && xyz && idx);
-    static const bool use_ballot = !(getenv("CMF_BALL_QUERY_BALLOT") && getenv("CMF_BALL_QUERY_BALLOT")[0] == '0');
+    static const bool use_ballot = cmf_env_on("CMF_BALL_QUERY_BALLOT");
     if (use_ballot && n > 0 && n <= BQB_MAX_N && nsample <= 256)
         return ball_query_ballot(b, n, m, radius, nsample, 1, new_xyz, xyz, idx, (hipStream_t)stream);
     if (ball_query_grid_takes(n, radius)) return ball_query_grid(b, n, m, radius, nsample, new_xyz, xyz, idx, (hipStream_t)stream, 1);
@@ -711,7 +711,7 @@ extern "C" int cmf_ball_query(int b, int n, int m, float radius, int nsample,
     CMF_CHECK_ARG(new_xyz && xyz && idx);
     if (ball_query_grid_takes(n, radius)) return ball_query_grid(b, n, m, radius, nsample, new_xyz, xyz, idx, (hipStream_t)stream);
     // small clouds: the ballot kernel (CMF_BALL_QUERY_BALLOT=0 keeps the scan kernels: diagnostics)
-    static const bool use_ballot = !(getenv("CMF_BALL_QUERY_BALLOT") && getenv("CMF_BALL_QUERY_BALLOT")[0] == '0');
+    static const bool use_ballot = cmf_env_on("CMF_BALL_QUERY_BALLOT");
     if (use_ballot && n <= BQB_MAX_N && nsample <= 256)
         return ball_query_ballot(b, n, m, radius, nsample, 0, new_xyz, xyz, idx, (hipStream_t)stream);
     dim3 grid(cmf_divup(m, CMF_WAVE), b);

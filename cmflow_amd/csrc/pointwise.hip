@@ -937,8 +937,6 @@ int cmf_bn_relu_maxpool_batch(int n, CmfPoolArgs *a, hipStream_t st)
     return cmf_launch_status();
 }
 
-int cmf_bn_relu_maxpool_sel(long long P, int S, int C, const float *z, const float *a, const float *c,
-                            float *out, long long ldo, unsigned char *argmax, float *zsel, void *stream);
 extern "C" int cmf_bn_relu_maxpool(long long P, int S, int C, const float *z, const float *a, const float *c,
                                    float *out, long long ldo, unsigned char *argmax, void *stream)
 {

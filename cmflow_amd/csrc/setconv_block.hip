@@ -5,19 +5,37 @@
 // Issued one by one from Python (ctypes call + tensor allocations + autograd bookkeeping, ~10-15 us each)
 // the first encoder of the model was entirely host bound (1.3 ms per call for ~0.2 ms of GPU work).  Here the
 // whole sequence is enqueued from C++ into caller-provided arenas; the kernels and their order are exactly
-// those of cmflow_amd/fused_blocks.py (SetConvFn), which remains the readable specification.
+// those of cmflow_amd/fused_blocks.py's SetConvFn (and MLPChainFn for cmf_mlp_forward / _backward at the end of the
+// file), which remain the readable specification.  The product calls arrive from the same module: SetConvBlockFn (one
+// block), MultiScaleBlockFn / DualCloudBlockFn (the blocks of an encoder call: queries, heads / bodies on the stream
+// pool or batched, batched tails) and MLPChainBlockFn, with descriptors filled by _fill_setconv_desc / _fill_bn.
+//
+// In code a layer is the index l of the BatchNorm it ends in, as in the descriptor's arrays: l = 0 the hoisted first conv,
+// 1 .. 2 per neighbour slot (M = B N S rows), the max over the ball, 3 .. 5 per point (P = B N rows); conv layer l (1 .. 5)
+// has weights d->w[l - 1].  The prose counts from one as the reference does ("layers 4-6" = l = 3 .. 5).
 #include <algorithm>
+#include <condition_variable>
 #include <cstdint>
-#include <cstdlib>
+#include <functional>
+#include <mutex>
+#include <thread>
+#include <vector>
 #include "cmf_common.h"
 #include "gemm_args.h"
 #include "../../include/cmflow_hip.h"
 
-bool cmf_setconv_chain_supported(int N, int S, int O1, int C2, int C3, long long M);
-long long cmf_setconv_chain_waves(long long M, int backward);
-bool cmf_ball_query_multi_takes(int n, int nq, const int *nsamples);      // csrc/neighbor.hip
-
 namespace {
+
+#define CMF_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
+
+// the A/B switches of this file (each on unless its variable starts with '0')
+inline bool thin_fused_on() { static const bool on = cmf_env_on("CMF_THIN_FUSED"); return on; }
+inline bool thin_wide_on() { static const bool on = cmf_env_on("CMF_THIN_WIDE"); return on; }
+inline bool body_batch_on() { static const bool on = cmf_env_on("CMF_BODY_BATCH"); return on; }
+inline bool tail_batch_on() { static const bool on = cmf_env_on("CMF_TAIL_BATCH"); return on; }
+inline bool train_gather_on() { static const bool on = cmf_env_on("CMF_TRAIN_GATHER"); return on; }
+inline bool train_gather_sum_on() { static const bool on = cmf_env_on("CMF_TRAIN_GATHER_SUM"); return on; }
+inline bool bnb_gather_on() { static const bool on = cmf_env_on("CMF_BNB_GATHER"); return on; }
 
 // training through the register chain (csrc/setconv_chain.hip): the narrow block's slot-level activations z1 / z2 / z3 are never stored
 // -- every pass recomputes them from the gathered per-point rows; z3's slot of `saved` holds the selected pre-activations (P x C3).
@@ -78,22 +96,42 @@ inline int dw_split(long long M, int N, int K)
     return best;
 }
 
+// One layer's folded BatchNorm block in `saved`: mean | invstd | a | c (4 * C floats; y = relu(a z + c)).  The only host code
+// that spells the order out.  All null: no BatchNorm in front (an input that is already active).
+struct Bn {
+    float *mean, *invstd, *a, *c;
+    Bn() : mean(nullptr), invstd(nullptr), a(nullptr), c(nullptr) {}
+    Bn(float *block, int C) : mean(block), invstd(block ? block + C : nullptr), a(block ? block + 2 * C : nullptr), c(block ? block + 3 * C : nullptr) {}
+    float *block() const { return mean; }         // the whole block (the fold kernels and the register chain address it themselves)
+};
+
 struct Layout {
     // saved for backward
     int *idx, *offsets, *inv;
     float *dxyz, *z1, *z2, *z3, *x, *z4, *z5, *z6, *fwd_sums;
     unsigned char *argmax;
     float *zsel;                  // (P, C3) pre-activations of layer 3 at the arg-max slots (per-layer path; the chain keeps them in z3's slot)
-    float *bn[6];                 // per layer: mean | invstd | a | c   (4 * C_l)
+    Bn bn[6];
     // scratch
     float *partial, *partial_x, *sums, *t6, *t5, *t4, *dx, *dU3, *dU2, *dU1, *splitk;
     float *dZ2;                   // dZ of BN layer 1, written by the gathering weight-gradient GEMM that fuses its BN backward (or null)
     size_t saved_floats, scratch_floats;
+    // per layer l = 0 .. 5: the pre-activations of BN layer l and the gradient with respect to them; per conv layer l = 1 .. 5: its
+    // input, the BatchNorm in front of it and the gradient into that input (l = 3 reads the pooled rows x, already active)
+    float *z(int l) const { float *const v[6] = {z1, z2, z3, z4, z5, z6}; return v[l]; }
+    float *dU(int l) const { float *const v[6] = {dU1, dU2, dU3, t4, t5, t6}; return v[l]; }
+    float *zin(int l) const { return l == 3 ? x : z(l - 1); }
+    float *dUin(int l) const { return l == 3 ? dx : dU(l - 1); }
+    Bn bn_in(int l) const { return l == 3 ? Bn() : bn[l - 1]; }
 };
 
 inline int chan(const cmf_setconv_desc *d, int layer)       // out channels of BN layer 0..5
 {
     return layer == 0 ? d->O1 : d->C[layer - 1];
+}
+inline long long rows_of(const cmf_setconv_desc *d, int layer)      // rows of BN layer 0..5: neighbour slots, behind the max points
+{
+    return (long long)d->B * d->N * (layer <= 2 ? d->S : 1);
 }
 
 // The arenas are sized by PATH (VERDICT r5 item 7 / ADVICE r4).  A block that never materialises its grouped first-layer tensor
@@ -108,17 +146,20 @@ inline int chan(const cmf_setconv_desc *d, int layer)       // out channels of B
 // backward call wants the input gradient (d->dy set) is the CALL's business: the backward entry points pass it to make_layout,
 // cmf_setconv_sizes reports the scratch size of either case and reads no output pointer.
 // CMF_TRAIN_GATHER=0 / CMF_TRAIN_GATHER_SUM=0 (A/B) bring the materialised sizes back.
+//
+// gather_layout -- training without the grouped first-layer tensor (second-encoder shapes, train-mode or eval-mode BatchNorm alike): the
+// forward pass takes the layer's statistics from cmf_group_affine's statistics-only form and the three GEMMs that read the tensor form
+// it from the per-point rows (cmf_gemm_gather_affine / cmf_gemm_dx_gather / cmf_gemm_dw_gather: each bit-identical to its materialised
+// counterpart).  The slot is sized for the gathering form, so there is no other form to fall back to.
+// gather_sum_layout -- ... and, when the input gradient is wanted, without the data gradient into the first layer either (M x O1 again):
+// the GEMM walks the slots in inverse-index order and reduces runs of equal source points in its epilogue (cmf_gemm_dx_gather_sum); the
+// scatter at the end of the block adds a point's pieces.
 inline bool gather_layout(const cmf_setconv_desc *d)
 {
-    static const bool on = !(getenv("CMF_TRAIN_GATHER") && getenv("CMF_TRAIN_GATHER")[0] == '0');
     const long long M = (long long)d->B * d->N * d->S;
-    return on && M % 128 == 0 && M < (1ll << 31) && d->C[0] % 128 == 0 && d->O1 % 128 == 0 && d->ldy % 4 == 0;
+    return train_gather_on() && M % 128 == 0 && M < (1ll << 31) && d->C[0] % 128 == 0 && d->O1 % 128 == 0 && d->ldy % 4 == 0;
 }
-inline bool gather_sum_shape(const cmf_setconv_desc *d)
-{
-    static const bool on = !(getenv("CMF_TRAIN_GATHER_SUM") && getenv("CMF_TRAIN_GATHER_SUM")[0] == '0');
-    return on && gather_layout(d) && d->S >= 2;
-}
+inline bool gather_sum_shape(const cmf_setconv_desc *d) { return train_gather_sum_on() && gather_layout(d) && d->S >= 2; }
 inline bool gather_sum_layout(const cmf_setconv_desc *d) { return gather_sum_shape(d) && d->dy != nullptr; }   // of a backward call
 
 // BN backward of the layer behind the gathered first layer inside its weight-gradient GEMM (cmf_gemm_dw_gather_bn_bwd): the stand-alone
@@ -129,8 +170,7 @@ inline bool gather_sum_layout(const cmf_setconv_desc *d) { return gather_sum_sha
 // left opt-in for: the step is the figure of merit.]  CMF_BNB_GATHER=0: the stand-alone pass (A/B).
 inline bool bnb_gather(const cmf_setconv_desc *d)
 {
-    static const bool on = !(getenv("CMF_BNB_GATHER") && getenv("CMF_BNB_GATHER")[0] == '0');
-    return on && d->training && gather_layout(d) && ((long long)d->B * d->N * d->S) >= 32768;
+    return bnb_gather_on() && d->training && gather_layout(d) && ((long long)d->B * d->N * d->S) >= 32768;
 }
 
 // sum_in_gemm (backward only): the call produces the input gradient, so a gather_sum_shape block sums the first layer's data gradient
@@ -154,7 +194,7 @@ Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool
     L.z5 = s.take(P * C5);
     L.z6 = s.take(P * C6);
     L.fwd_sums = s.take(3 * O1 + 4);
-    for (int l = 0; l < 6; ++l) L.bn[l] = s.take(4 * (size_t)chan(d, l));
+    for (int l = 0; l < 6; ++l) L.bn[l] = Bn(s.take(4 * (size_t)chan(d, l)), chan(d, l));
     L.zsel = s.take(P * C3);       // (behind everything else: the offsets of the older slots are part of the Python side's contract)
     L.saved_floats = s.off;
 
@@ -195,30 +235,6 @@ Layout make_layout(const cmf_setconv_desc *d, float *saved, float *scratch, bool
     return L;
 }
 
-#define CMF_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
-
-}  // namespace
-// csrc/setconv_chain.hip (internal): the narrow block's neighbour-slot layers as register-chain passes with eval-mode BN
-// (mode: 0 inference, 1 max over the ball + argmax + selected pre-activations, 2 / 3 backward of layers 3 / 2)
-bool cmf_setconv_chain_supported(int N, int S, int O1, int C2, int C3, long long M);
-long long cmf_setconv_chain_waves(long long M, int backward);
-int cmf_setconv_chain_pass(int mode, long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
-                           long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
-                           long long ldo, float *zsel, unsigned char *argmax, float *partial, const float *g, const float *dU_in, float *dU_out,
-                           float *slabs, void *stream);
-// csrc/pointwise.hip (internal)
-int cmf_bn_relu_maxpool_sel(long long P, int S, int C, const float *z, const float *a, const float *c, float *out, long long ldo,
-                            unsigned char *argmax, float *zsel, void *stream);
-void cmf_gemm_dx_gather_sum_hint(long long points);
-int cmf_maxpool_bwd_point_sel(long long P, int C, const float *dout, long long ldd, const float *zsel, const float *a, const float *c,
-                              const float *mean, const float *invstd, float *g, float *partial, void *stream);
-int cmf_setconv_chain_infer(long long M, int N, int S, const int *idx, const float *xyz, const float *y, long long ldy, const float *wx,
-                            long long ldwx, const float *bn0, const float *bn1, const float *bn2, const float *w2, const float *w3, float *out,
-                            long long ldo, void *stream);
-// csrc/pointwise.hip (internal): cmf_colsum with the first 2*C columns stored to dst0 / dst1
-int cmf_colsum_store(int tiles, int ncols, const float *partial, float *out, int C, float *dst0, float *dst1, void *stream);
-namespace {
-
 // Eval mode: the six folds depend on nothing the block computes (running statistics), so they are ONE launch at the head
 // of the chain instead of six tiny kernels between its GEMMs.  Same arithmetic as bn_finalize_kernel's eval branch.
 struct FoldAll { int C[6]; const float *gamma[6], *beta[6], *rmean[6], *rvar[6]; float eps[6]; float *out[6]; };
@@ -250,108 +266,188 @@ __global__ __launch_bounds__(256) void bn_fold_eval_batch_kernel(const CmfBatch<
     }
 }
 
-int fold_all_eval(const cmf_setconv_desc *d, const Layout &L, void *st)
+FoldAll fold_all_args(const cmf_setconv_desc *d, const Layout &L)
 {
     FoldAll f;
     for (int l = 0; l < 6; ++l) {
-        CMF_CHECK_ARG(d->rmean[l] && d->rvar[l]);
         f.C[l] = chan(d, l); f.gamma[l] = d->gamma[l]; f.beta[l] = d->beta[l]; f.rmean[l] = d->rmean[l]; f.rvar[l] = d->rvar[l];
-        f.eps[l] = d->eps[l]; f.out[l] = L.bn[l];
+        f.eps[l] = d->eps[l]; f.out[l] = L.bn[l].block();
     }
-    hipLaunchKernelGGL(bn_fold_eval_kernel, dim3(6), dim3(256), 0, (hipStream_t)st, f);
+    return f;
+}
+
+int fold_all_eval(const cmf_setconv_desc *d, const Layout &L, void *st)
+{
+    for (int l = 0; l < 6; ++l) CMF_CHECK_ARG(d->rmean[l] && d->rvar[l]);
+    hipLaunchKernelGGL(bn_fold_eval_kernel, dim3(6), dim3(256), 0, (hipStream_t)st, fold_all_args(d, L));
     return cmf_launch_status();
 }
 
-// BN fold of layer l from `partial` (train: batch statistics + running-stat update) into L.bn[l]; eval: done up front
-int fold(const cmf_setconv_desc *d, const Layout &L, int l, long long rows, void *st)
+// ---- one builder per argument block ----------------------------------------------------------------------------------
+// The batched loops collect the structs; a single launch hands the same struct's fields to the positional entry point (never to
+// a _batch entry point with n = 1: that is another kernel).  D: cmf_setconv_desc or cmf_mlp_desc.
+
+// BN fold of layer l from `rows` rows' statistics in `partial` (train mode: batch statistics + running-statistics update)
+template <class D> CmfBnFinArgs bn_fin_args(const D *d, int l, long long rows, int C, const float *partial, const Bn &b)
 {
-    if (!d->training) return 0;
-    const int C = chan(d, l);
-    float *b = L.bn[l];
-    return cmf_bn_finalize(tiles128(rows), C, (double)rows, L.partial, d->gamma[l], d->beta[l], d->eps[l], d->momentum[l],
-                           d->rmean[l], d->rvar[l], b, b + C, b + 2 * C, b + 3 * C, d->nbt[l], st);
+    return CmfBnFinArgs{tiles128(rows), C, (double)rows, partial, d->gamma[l], d->beta[l], d->eps[l], d->momentum[l], d->rmean[l], d->rvar[l],
+                        b.mean, b.invstd, b.a, b.c, d->nbt[l]};
+}
+int bn_finalize(const CmfBnFinArgs &f, void *st)
+{
+    return cmf_bn_finalize(f.tiles, f.C, f.count, f.partial, f.gamma, f.beta, f.eps, f.momentum, f.rmean, f.rvar, f.mean_out, f.invstd_out,
+                           f.a_out, f.c_out, f.nbt, st);
+}
+CmfBnFinArgs fold_args(const cmf_setconv_desc *d, const Layout &L, int l) { return bn_fin_args(d, l, rows_of(d, l), chan(d, l), L.partial, L.bn[l]); }
+// (eval mode: the folds were done up front by fold_all_eval -- which is what makes the three exits of the forward one sequence)
+int fold(const cmf_setconv_desc *d, const Layout &L, int l, void *st) { return d->training ? bn_finalize(fold_args(d, L, l), st) : 0; }
+
+// dgamma / dbeta of BN layer l: the column sums of `tiles` rows of BN-backward partials (ncols = 2 C; the first layer's 5 C with the
+// dW_xyz sums behind them), accumulated into the gradient buffers or stored there
+template <class D> CmfColsumArgs bn_grad_args(const D *d, int l, int tiles, int ncols, int C, const float *partial, float *sums)
+{
+    return CmfColsumArgs{tiles, ncols, partial, sums, C, d->dbeta[l], d->dgamma[l], d->acc_bn[l] ? 0 : 1};
+}
+int bn_grad_sums(const CmfColsumArgs &c, void *st)
+{
+    if (c.store) return cmf_colsum_store(c.tiles, c.ncols, c.partial, c.out, c.C, c.acc0, c.acc1, st);
+    return cmf_colsum(c.tiles, c.ncols, c.partial, c.out, c.C, c.acc0, c.acc1, st);
+}
+CmfColsumArgs bn_grad_args(const cmf_setconv_desc *d, const Layout &L, int l, int tiles)
+{
+    return bn_grad_args(d, l, tiles, (l == 0 ? 5 : 2) * chan(d, l), chan(d, l), L.partial, L.sums);
 }
 
-// Z_out = act_{l_in}(Z_in) @ W^T (+ statistics), Z_in activated by BN layer l_in (or already active if l_in < 0)
-int fwd_gemm(const cmf_setconv_desc *d, const Layout &L, long long rows, int cin, int cout, const float *zin, int l_in,
-             const float *w, float *zout, void *st)
+// y = relu(a z + c) behind the last layer, and its backward dU = dY * mask with the BN-backward partials
+CmfAffineArgs affine_args(long long rows, int C, const float *z, const Bn &b, float *out, long long ldo)
 {
-    const float *pa = l_in >= 0 ? L.bn[l_in] + 2 * chan(d, l_in) : nullptr;
-    const float *pc = l_in >= 0 ? L.bn[l_in] + 3 * chan(d, l_in) : nullptr;
-    return cmf_gemm((int)rows, cout, cin, 0, 1, zin, cin, w, cin, zout, cout, pa, pc, nullptr, nullptr, nullptr, 0,
-                    d->training ? L.partial : nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0, st);
+    return CmfAffineArgs{rows, C, z, C, b.a, b.c, out, ldo};
+}
+int affine_relu(const CmfAffineArgs &a, void *st) { return cmf_affine_relu(a.M, a.C, a.z, a.ldz, a.a, a.c, a.out, a.ldo, st); }
+CmfAffineArgs out_args(const cmf_setconv_desc *d, const Layout &L) { return affine_args(rows_of(d, 5), chan(d, 5), L.z6, L.bn[5], d->out, d->ldo); }
+
+CmfActBwdArgs act_bwd_args(long long rows, int C, const float *dY, long long ldy, const float *z, const Bn &b, float *dU, float *partial)
+{
+    return CmfActBwdArgs{rows, C, dY, ldy, z, C, b.a, b.c, b.mean, b.invstd, dU, partial};
+}
+int act_bwd(const CmfActBwdArgs &a, void *st)
+{
+    return cmf_act_bwd_stats(a.rows, a.C, a.dY, a.ldy, a.z, a.ldz, a.a, a.c, a.mean, a.invstd, a.dU, a.partial, st);
+}
+CmfActBwdArgs dout_args(const cmf_setconv_desc *d, const Layout &L)
+{
+    return act_bwd_args(rows_of(d, 5), chan(d, 5), d->dout, d->lddout, L.z6, L.bn[5], L.t6, L.partial);
 }
 
-// dW[cout,cin] (+)= dZ^T @ act_{l_in}(X)
-int dw_gemm(const cmf_setconv_desc *d, const Layout &L, long long rows, int cout, int cin, const float *dZ, const float *x, int l_in,
-            float *dw, int accumulate, void *st)
+// ---- the three GEMMs of a layer: the only cmf_gemm calls of this file -------------------------------------------------
+// Z_out = act_in(Z_in) @ W^T (+ statistics of Z_out into `stats`), Z_in (row pitch ldin) activated by the BatchNorm `in` in front
+GemmArgs fwd_gemm_args(long long rows, int cin, int cout, const float *zin, long long ldin, const Bn &in, const float *w, float *zout,
+                       float *stats)
+{
+    GemmArgs q{};
+    q.M = (int)rows; q.N = cout; q.K = cin; q.A = zin; q.lda = ldin; q.B = w; q.ldb = cin; q.C = zout; q.ldc = cout;
+    q.pro_a = in.a; q.pro_c = in.c; q.stats = stats; q.split_k = 1;
+    return q;
+}
+int fwd_gemm(const GemmArgs &q, void *st)
+{
+    return cmf_gemm(q.M, q.N, q.K, 0, 1, q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.pro_a, q.pro_c, nullptr, nullptr, nullptr, 0, q.stats, 0,
+                    nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, q.split_k, nullptr, 0, st);
+}
+// conv layer l = 1 .. 5 of a block
+GemmArgs fwd_layer(const cmf_setconv_desc *d, const Layout &L, int l)
+{
+    const int cin = chan(d, l - 1);
+    return fwd_gemm_args(rows_of(d, l), cin, chan(d, l), L.zin(l), cin, L.bn_in(l), d->w[l - 1], L.z(l), d->training ? L.partial : nullptr);
+}
+
+// dW[cout, cin] (+)= dZ^T @ act_in(X), X with row pitch ldx; deterministic split-K through `splitk`
+int dw_gemm(long long rows, int cout, int cin, const float *dZ, const float *x, long long ldx, const Bn &in, float *dw, int accumulate,
+            float *splitk, void *st)
 {
     if (!dw) return 0;
-    const float *pa = l_in >= 0 ? L.bn[l_in] + 2 * chan(d, l_in) : nullptr;
-    const float *pc = l_in >= 0 ? L.bn[l_in] + 3 * chan(d, l_in) : nullptr;
     const int split = dw_split(rows, cout, cin);
-    return cmf_gemm(cout, cin, (int)rows, 1, 0, dZ, cout, x, cin, dw, cin, nullptr, nullptr, pa, pc, nullptr, 0, nullptr, 0,
-                    nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, split, split > 1 ? L.splitk : nullptr, accumulate, st);
+    return cmf_gemm(cout, cin, (int)rows, 1, 0, dZ, cout, x, ldx, dw, cin, nullptr, nullptr, in.a, in.c, nullptr, 0, nullptr, 0,
+                    nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, split, split > 1 ? splitk : nullptr, accumulate, st);
 }
-
-// dU_x = (dZ @ W) masked by x's BN+ReLU (layer l_x), with the BN-backward partial sums (and the dxyz sums when q != 0)
-int dx_gemm(const cmf_setconv_desc *d, const Layout &L, long long rows, int cout, int cin, const float *dZ, const float *w,
-            const float *x, int l_x, float *dU, const float *dxyz, void *st)
+// dU_x (row pitch lddu) = dZ @ W, masked by the BN + ReLU `in` of x with the BN-backward partials into `stats` (and the dxyz sums when
+// dxyz is given); no BatchNorm in front of x: the plain product
+int dx_gemm(long long rows, int cout, int cin, const float *dZ, const float *w, float *dU, long long lddu, const float *x, const Bn &in,
+            float *stats, const float *dxyz, void *st)
 {
-    if (l_x < 0)
-        return cmf_gemm((int)rows, cin, cout, 0, 0, dZ, cout, w, cin, dU, cin, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                        0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0, st);
-    const int C = chan(d, l_x);
-    const float *b = L.bn[l_x];
-    return cmf_gemm((int)rows, cin, cout, 0, 0, dZ, cout, w, cin, dU, cin, nullptr, nullptr, nullptr, nullptr, nullptr, 0, L.partial,
-                    1, x, cin, b + 2 * C, b + 3 * C, b, b + C, dxyz, 1, nullptr, 0, st);
+    const bool mask = in.a != nullptr;
+    return cmf_gemm((int)rows, cin, cout, 0, 0, dZ, cout, w, cin, dU, lddu, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                    mask ? stats : nullptr, mask ? 1 : 0, mask ? x : nullptr, mask ? cin : 0, in.a, in.c, in.mean, in.invstd,
+                    mask ? dxyz : nullptr, 1, nullptr, 0, st);
 }
 
-// One backward layer: the BN-backward sums of layer l_out (dgamma / dbeta), then dZ -> dW (+ dU of the layer below).
+// the backward of conv layer l = 1 .. 5 behind BN layer l as the fused single-pass kernel's argument block (nslab: the batch call's)
+CmfThinBwdCall bwd_layer_args(const cmf_setconv_desc *d, const Layout &L, int l)
+{
+    const int cout = chan(d, l), cin = chan(d, l - 1);
+    const Bn b = L.bn[l], in = L.bn_in(l);
+    CmfThinBwdCall q{};
+    q.rows = rows_of(d, l); q.cout = cout; q.cin = cin; q.dU = L.dU(l); q.lddu = cout; q.z = L.z(l); q.ldz = cout;
+    q.a = b.a; q.mean = b.mean; q.invstd = b.invstd; q.sums = d->training ? L.sums : nullptr;
+    q.w = d->w[l - 1]; q.ldw = cin; q.x = L.zin(l); q.ldx = cin; q.in_mode = l != 3 ? 1 : 0;
+    q.a_in = in.a; q.c_in = in.c; q.mean_in = in.mean; q.invstd_in = in.invstd; q.dxyz = l == 1 ? L.dxyz : nullptr;
+    q.dx = L.dUin(l); q.lddx = cin; q.stats = l != 3 ? L.partial : nullptr;
+    q.dw = d->dw[l - 1]; q.lddw = cin; q.accumulate = d->acc_w[l - 1]; q.slabs = L.splitk;
+    return q;
+}
+// the slab sum behind a batched launch of such layers
+CmfSplitkArgs splitk_args(const CmfThinBwdCall &q) { return CmfSplitkArgs{q.cout, q.cin, q.nslab, q.slabs, q.dw, q.lddw, q.accumulate}; }
+
+// One backward layer: the BN-backward sums of layer l (dgamma / dbeta), then dZ -> dW (+ dU of the layer below).
 // Narrow layers run the fused single-pass kernel (cmf_thin_bwd_layer: dZ is never stored); the wide ones of the second
 // encoder the BN backward in place followed by the two tiled GEMMs.  CMF_THIN_FUSED=0 forces the three-kernel form.
-int bwd_layer(const cmf_setconv_desc *d, const Layout &L, int l_out, long long rows, int cout, int cin, float *dU, const float *z_out,
-              const float *w, const float *x, int l_in, float *dU_in, const float *dxyz, float *dw, int acc_w, void *st)
+int bwd_layer(const cmf_setconv_desc *d, const Layout &L, int l, void *st)
 {
-    const float *b = L.bn[l_out];
-    if (d->acc_bn[l_out]) CMF_TRY(cmf_colsum_finalize(tiles128(rows), cout, L.partial, L.sums, d->dbeta[l_out], d->dgamma[l_out], st));
-    else CMF_TRY(cmf_colsum_store(tiles128(rows), 2 * cout, L.partial, L.sums, cout, d->dbeta[l_out], d->dgamma[l_out], st));
-    static const bool fused = !(getenv("CMF_THIN_FUSED") && getenv("CMF_THIN_FUSED")[0] == '0');
-    if (fused && cmf_thin_bwd_supported(cout, cin)) {
-        const float *bi = l_in >= 0 ? L.bn[l_in] : nullptr;
-        const int ci = l_in >= 0 ? chan(d, l_in) : 0;
-        return cmf_thin_bwd_layer(rows, cout, cin, dU, cout, z_out, cout, b + 2 * cout, b, b + cout, d->training ? L.sums : nullptr,
-                                  w, cin, x, cin, l_in >= 0 ? 1 : 0, bi ? bi + 2 * ci : nullptr, bi ? bi + 3 * ci : nullptr, bi,
-                                  bi ? bi + ci : nullptr, dxyz, dU_in, cin, l_in >= 0 ? L.partial : nullptr, dw, cin, acc_w, L.splitk, st);
-    }
-    CMF_TRY(cmf_bn_bwd_apply(rows, cout, dU, z_out, cout, b + 2 * cout, b, b + cout, d->training ? L.sums : nullptr, st));
-    CMF_TRY(dw_gemm(d, L, rows, cout, cin, dU, x, l_in, dw, acc_w, st));
-    return dx_gemm(d, L, rows, cout, cin, dU, w, x, l_in, dU_in, dxyz, st);
+    const CmfThinBwdCall q = bwd_layer_args(d, L, l);
+    CMF_TRY(bn_grad_sums(bn_grad_args(d, L, l, tiles128(q.rows)), st));
+    if (thin_fused_on() && cmf_thin_bwd_supported(q.cout, q.cin))
+        return cmf_thin_bwd_layer(q.rows, q.cout, q.cin, q.dU, q.lddu, q.z, q.ldz, q.a, q.mean, q.invstd, q.sums, q.w, q.ldw, q.x, q.ldx,
+                                  q.in_mode, q.a_in, q.c_in, q.mean_in, q.invstd_in, q.dxyz, q.dx, q.lddx, q.stats, q.dw, q.lddw, q.accumulate,
+                                  q.slabs, st);
+    float *dZ = L.dU(l);                                            // in place
+    CMF_TRY(cmf_bn_bwd_apply(q.rows, q.cout, dZ, q.z, q.ldz, q.a, q.mean, q.invstd, q.sums, st));
+    CMF_TRY(dw_gemm(q.rows, q.cout, q.cin, dZ, q.x, q.ldx, L.bn_in(l), q.dw, q.accumulate, q.slabs, st));
+    return dx_gemm(q.rows, q.cout, q.cin, dZ, q.w, q.dx, q.lddx, q.x, L.bn_in(l), q.stats, q.dxyz, st);
 }
 
-// Training without the grouped first-layer tensor (second-encoder shapes; CMF_TRAIN_GATHER=0 keeps the tensor: A/B): the forward pass takes the layer's
-// statistics from cmf_group_affine's statistics-only form and the three GEMMs that read the tensor form it from the per-point rows
-// (cmf_gemm_gather_affine / cmf_gemm_dx_gather / cmf_gemm_dw_gather: each bit-identical to its materialised counterpart); the
-// tensor's slot in `saved` holds the row indices and the coordinate planes of Wx.
-bool train_gather(const cmf_setconv_desc *d)
+// the per-point tail of a block, forward (l = 3 .. 5 and the output activation) and backward (down to Layout::dx)
+int forward_tail(const cmf_setconv_desc *d, const Layout &L, void *st)
 {
-    // (train-mode or eval-mode BatchNorm alike: with eval-mode statistics -- the regime of every epoch after the first in the reference's
-    //  training loop -- the forward pass is the inference form and the backward pass the same two gathering GEMMs)
-    // = the layout predicate: the slot of the tensor is sized for the gathering form, there is no other form to fall back to
-    return gather_layout(d);
+    for (int l = 3; l < 6; ++l) {
+        CMF_TRY(fwd_gemm(fwd_layer(d, L, l), st));
+        CMF_TRY(fold(d, L, l, st));
+    }
+    return affine_relu(out_args(d, L), st);
 }
+int backward_tail(const cmf_setconv_desc *d, const Layout &L, void *st)
+{
+    CMF_TRY(act_bwd(dout_args(d, L), st));
+    for (int l = 5; l >= 3; --l) CMF_TRY(bwd_layer(d, L, l, st));
+    return 0;
+}
+
+// the head of the backward's pooled-gradient branches: the gradient of the max over the ball kept per POINT (g = L.dU3) with the
+// BN-backward partials of l = 2 from the pre-activations at the arg-max slots (zsel), then that layer's dgamma / dbeta
+int pooled_grad_head(const cmf_setconv_desc *d, const Layout &L, const float *zsel, void *st)
+{
+    const Bn &b = L.bn[2];
+    const long long P = rows_of(d, 3);
+    const int C3 = chan(d, 2);
+    CMF_TRY(cmf_maxpool_bwd_point_sel(P, C3, L.dx, C3, zsel, b.a, b.c, b.mean, b.invstd, L.dU3, L.partial, st));
+    return bn_grad_sums(bn_grad_args(d, L, 2, tiles128(P)), st);
+}
+
 // the gathering kernels' 16-byte loads: with the compact layout a misaligned operand is an argument error, not a fallback
 bool gather_operands_aligned(const cmf_setconv_desc *d) { return (((uintptr_t)d->y | (uintptr_t)d->w[0]) & 15) == 0; }
 int *gather_rows(const Layout &L) { return reinterpret_cast<int *>(L.z1); }
 float *gather_wx3(const Layout &L, long long M) { return L.z1 + (M + 3) / 4 * 4; }
 
-// bwd_layer for the layer behind the gathered first layer: BN-backward sums, BN backward in place, weight gradient and masked data
-// gradient with the first layer formed in their operand / epilogue paths
-// ... and, when the input gradient is wanted, without the data gradient into the first layer either (M x O1 again): the GEMM walks the
-// slots in inverse-index order and reduces runs of equal source points in its epilogue (cmf_gemm_dx_gather_sum); the scatter at the end
-// of the block adds a point's pieces.  CMF_TRAIN_GATHER_SUM=0 keeps the stored gradient (A/B).  The slot of dU1 holds the pieces, the
-// permutation, the permuted source points and relative coordinates.
-bool train_gather_sum(const cmf_setconv_desc *d) { return gather_sum_layout(d); }
+// gather_sum_layout: the slot of dU1 holds the pieces, the permutation, the permuted source points and relative coordinates
 struct SumSlots { float *pieces; int *perm, *pts; float *dq2; };
 SumSlots sum_slots(const cmf_setconv_desc *d, const Layout &L)
 {
@@ -364,35 +460,37 @@ SumSlots sum_slots(const cmf_setconv_desc *d, const Layout &L)
     return s;
 }
 
-int bwd_layer1_gather(const cmf_setconv_desc *d, const Layout &L, long long M, int C2, int O1, void *st)
+// bwd_layer for the layer behind the gathered first layer: BN-backward sums, BN backward in place, weight gradient and masked data
+// gradient with the first layer formed in their operand / epilogue paths
+int bwd_layer1_gather(const cmf_setconv_desc *d, const Layout &L, void *st)
 {
-    const float *b = L.bn[1], *b0 = L.bn[0];
-    if (d->acc_bn[1]) CMF_TRY(cmf_colsum_finalize(tiles128(M), C2, L.partial, L.sums, d->dbeta[1], d->dgamma[1], st));
-    else CMF_TRY(cmf_colsum_store(tiles128(M), 2 * C2, L.partial, L.sums, C2, d->dbeta[1], d->dgamma[1], st));
+    const long long M = rows_of(d, 1);
+    const int O1 = d->O1, C2 = d->C[0];
+    const Bn &b = L.bn[1], &b0 = L.bn[0];
+    const int *rows = gather_rows(L);
+    const float *wx3 = gather_wx3(L, M);
+    const int split = dwg_split(M, C2, O1);
+    float *const slabs = split > 1 ? L.splitk : nullptr;
+    CMF_TRY(bn_grad_sums(bn_grad_args(d, L, 1, tiles128(M)), st));
     const float *dZ2 = L.dU2;
     if (bnb_gather(d) && L.dZ2 && d->dw[0]) {
-        const int split = dwg_split(M, C2, O1);
-        CMF_TRY(cmf_gemm_dw_gather_bn_bwd(C2, O1, M, L.dU2, C2, L.z2, C2, b + 2 * C2, b, b + C2, L.sums, L.dZ2, C2, d->y, d->ldy, gather_rows(L),
-                                          L.dxyz, gather_wx3(L, M), b0 + 2 * O1, b0 + 3 * O1, d->dw[0], O1, split, split > 1 ? L.splitk : nullptr,
-                                          d->acc_w[0], st));
+        CMF_TRY(cmf_gemm_dw_gather_bn_bwd(C2, O1, M, L.dU2, C2, L.z2, C2, b.a, b.mean, b.invstd, L.sums, L.dZ2, C2, d->y, d->ldy, rows, L.dxyz, wx3,
+                                          b0.a, b0.c, d->dw[0], O1, split, slabs, d->acc_w[0], st));
         dZ2 = L.dZ2;
     } else {
-    CMF_TRY(cmf_bn_bwd_apply(M, C2, L.dU2, L.z2, C2, b + 2 * C2, b, b + C2, d->training ? L.sums : nullptr, st));
-    if (d->dw[0]) {
-        const int split = dwg_split(M, C2, O1);
-        CMF_TRY(cmf_gemm_dw_gather(C2, O1, M, L.dU2, C2, d->y, d->ldy, gather_rows(L), L.dxyz, gather_wx3(L, M), b0 + 2 * O1, b0 + 3 * O1,
-                                   d->dw[0], O1, split, split > 1 ? L.splitk : nullptr, d->acc_w[0], st));
+        CMF_TRY(cmf_bn_bwd_apply(M, C2, L.dU2, L.z2, C2, b.a, b.mean, b.invstd, d->training ? L.sums : nullptr, st));
+        if (d->dw[0])
+            CMF_TRY(cmf_gemm_dw_gather(C2, O1, M, L.dU2, C2, d->y, d->ldy, rows, L.dxyz, wx3, b0.a, b0.c, d->dw[0], O1, split, slabs, d->acc_w[0], st));
     }
-    }
-    if (train_gather_sum(d)) {
+    if (gather_sum_layout(d)) {
         const SumSlots q = sum_slots(d, L);
-        CMF_TRY(cmf_group_perm(d->B, d->N * d->S, L.inv, gather_rows(L), L.dxyz, q.perm, q.pts, q.dq2, st));
+        CMF_TRY(cmf_group_perm(d->B, d->N * d->S, L.inv, rows, L.dxyz, q.perm, q.pts, q.dq2, st));
         cmf_gemm_dx_gather_sum_hint((long long)d->B * d->N);
-        return cmf_gemm_dx_gather_sum((int)M, O1, C2, dZ2, C2, d->w[0], O1, d->y, d->ldy, q.perm, q.pts, q.dq2, gather_wx3(L, M),
-                                      b0 + 2 * O1, b0 + 3 * O1, b0, b0 + O1, q.pieces, L.partial, st);
+        return cmf_gemm_dx_gather_sum((int)M, O1, C2, dZ2, C2, d->w[0], O1, d->y, d->ldy, q.perm, q.pts, q.dq2, wx3, b0.a, b0.c, b0.mean, b0.invstd,
+                                      q.pieces, L.partial, st);
     }
-    return cmf_gemm_dx_gather((int)M, O1, C2, dZ2, C2, d->w[0], O1, L.dU1, O1, d->y, d->ldy, gather_rows(L), L.dxyz, gather_wx3(L, M),
-                              b0 + 2 * O1, b0 + 3 * O1, b0, b0 + O1, L.partial, st);
+    return cmf_gemm_dx_gather((int)M, O1, C2, dZ2, C2, d->w[0], O1, L.dU1, O1, d->y, d->ldy, rows, L.dxyz, wx3, b0.a, b0.c, b0.mean, b0.invstd,
+                              L.partial, st);
 }
 
 }  // namespace
@@ -417,73 +515,53 @@ static int setconv_forward_part(const cmf_setconv_desc *d, void *st, int part)
     CMF_CHECK_ARG(!gather_layout(d) || gather_operands_aligned(d));
     const Layout L = make_layout(d, d->saved, d->scratch, false);
     const long long P = (long long)d->B * d->N, M = P * d->S;
-    const int O1 = d->O1, C2 = d->C[0], C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
+    const int O1 = d->O1, C2 = d->C[0], C3 = d->C[1];
+    const Bn &b0 = L.bn[0], &b2 = L.bn[2];
     // idx is pre-zeroed like the reference's BallQuery.forward (every point is its own neighbour here, but keep the contract)
     if (!d->training) CMF_TRY(fold_all_eval(d, L, st));
     if (!d->idx_ready) CMF_TRY(cmf_ball_query_defined(d->B, d->N, d->N, d->radius, d->S, d->xyz, d->xyz, L.idx, st));
-    // inference (eval-mode BN and no backward call to follow): the grouped first-layer tensor z1 (M x O1: 1 GB at the largest scale of
-    // the second encoder) is never written -- the second layer's GEMM gathers the per-point rows and forms the layer in its A-operand
-    // path (cmf_gemm_gather_affine, bit-identical); the slot of z1 holds the M source-row indices and the coordinate planes of Wx
-    // inference of the narrow block (first encoder): layers 1-3 and the max over the ball as ONE register-chain kernel
-    // (csrc/setconv_chain.hip; every layer bit-identical to the per-layer kernels) -- nothing but the pooled rows is written
+    // Three ways to the pooled rows L.x; the per-point tail behind them is the same sequence for all (eval mode: its folds are no-ops).
     if (!d->training && d->inference && cmf_setconv_chain_supported(d->N, d->S, O1, C2, C3, M) && d->ldy % 4 == 0 && ((uintptr_t)d->y & 15) == 0) {
-        CMF_TRY(cmf_setconv_chain_infer(M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
-                                        L.x, C3, st));
-        if (part == 1) return 0;
-        CMF_TRY(fwd_gemm(d, L, P, C3, C4, L.x, -1, d->w[2], L.z4, st));
-        CMF_TRY(fwd_gemm(d, L, P, C4, C5, L.z4, 3, d->w[3], L.z5, st));
-        CMF_TRY(fwd_gemm(d, L, P, C5, C6, L.z5, 4, d->w[4], L.z6, st));
-        return cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, st);
-    }
-    if (chain_train(d)) {
+        // inference of the narrow block (first encoder): layers 1-3 and the max over the ball as ONE register-chain kernel
+        // (csrc/setconv_chain.hip; every layer bit-identical to the per-layer kernels) -- nothing but the pooled rows is written
+        CMF_TRY(cmf_setconv_chain_infer(M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0].block(), L.bn[1].block(),
+                                        L.bn[2].block(), d->w[0], d->w[1], L.x, C3, st));
+    } else if (chain_train(d)) {
         // eval-mode BN with a backward pass to follow (one pass): nothing but the pooled rows, their argmax slots and the selected
         // pre-activations is stored
-        CMF_TRY(cmf_setconv_chain_pass(1, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0],
-                                       d->w[1], L.x, C3, L.z3, L.argmax, L.partial, nullptr, nullptr, nullptr, nullptr, st));
-        if (part == 1) return 0;
-        CMF_TRY(fwd_gemm(d, L, P, C3, C4, L.x, -1, d->w[2], L.z4, st));
-        CMF_TRY(fwd_gemm(d, L, P, C4, C5, L.z4, 3, d->w[3], L.z5, st));
-        CMF_TRY(fwd_gemm(d, L, P, C5, C6, L.z5, 4, d->w[4], L.z6, st));
-        return cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, st);
-    }
-    const bool gather = !d->training && ((d->inference && M % 128 == 0 && C2 % 128 == 0 && O1 % 16 == 0 && d->ldy % 4 == 0 &&
-                                          gather_operands_aligned(d) && M < (1ll << 31)) || train_gather(d));
-    if (d->training && train_gather(d)) {
-        CMF_TRY(cmf_group_affine(d->B, d->N, d->N, d->S, O1, d->y, (int)d->ldy, nullptr, 0, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, 0,
-                                 nullptr, L.dxyz, L.partial, L.partial_x, st));
-        CMF_TRY(cmf_colsum(tiles128(M), 3 * O1 + 4, L.partial_x, L.fwd_sums, 0, nullptr, nullptr, st));
-        CMF_TRY(fold(d, L, 0, M, st));
-        CMF_TRY(cmf_group_prep(d->B, d->N, d->N, d->S, O1, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, gather_rows(L), L.dxyz,
-                               gather_wx3(L, M), st));
-        CMF_TRY(cmf_gemm_gather_affine((int)M, C2, O1, d->y, d->ldy, gather_rows(L), L.dxyz, gather_wx3(L, M), L.bn[0] + 2 * O1,
-                                       L.bn[0] + 3 * O1, d->w[0], O1, L.z2, C2, L.partial, st));
-    } else
-    if (gather) {
-        int *rows = reinterpret_cast<int *>(L.z1);
-        float *wx3 = L.z1 + (M + 3) / 4 * 4;
-        CMF_TRY(cmf_group_prep(d->B, d->N, d->N, d->S, O1, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, rows, L.dxyz, wx3, st));
-        CMF_TRY(cmf_gemm_gather_affine((int)M, C2, O1, d->y, d->ldy, rows, L.dxyz, wx3, L.bn[0] + 2 * O1, L.bn[0] + 3 * O1, d->w[0], O1,
-                                       L.z2, C2, nullptr, st));
+        CMF_TRY(cmf_setconv_chain_pass(1, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0].block(), L.bn[1].block(),
+                                       L.bn[2].block(), d->w[0], d->w[1], L.x, C3, L.z3, L.argmax, L.partial, nullptr, nullptr, nullptr, nullptr, st));
     } else {
-    CMF_TRY(cmf_group_affine(d->B, d->N, d->N, d->S, O1, d->y, (int)d->ldy, nullptr, 0, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, 0,
-                             L.z1, L.dxyz, d->training ? L.partial : nullptr, d->training ? L.partial_x : nullptr, st));
-    if (d->training) CMF_TRY(cmf_colsum(tiles128(M), 3 * O1 + 4, L.partial_x, L.fwd_sums, 0, nullptr, nullptr, st));
-    CMF_TRY(fold(d, L, 0, M, st));
-    CMF_TRY(fwd_gemm(d, L, M, O1, C2, L.z1, 0, d->w[0], L.z2, st));
+        // gathering first layer: the grouped tensor z1 (M x O1: 1 GB at the largest scale of the second encoder) is never written -- the
+        // second layer's GEMM gathers the per-point rows and forms the layer in its A-operand path (cmf_gemm_gather_affine, bit-identical);
+        // the slot of z1 holds the M source-row indices and the coordinate planes of Wx.  Training on the compact layout (gather_layout),
+        // or inference (eval-mode BN and no backward call to follow) on shapes the kernel takes.
+        const bool gather = gather_layout(d) || (!d->training && d->inference && M % 128 == 0 && C2 % 128 == 0 && O1 % 16 == 0 &&
+                                                 d->ldy % 4 == 0 && gather_operands_aligned(d) && M < (1ll << 31));
+        if (gather) {
+            if (d->training) {                          // the layer's statistics from cmf_group_affine's statistics-only form
+                CMF_TRY(cmf_group_affine(d->B, d->N, d->N, d->S, O1, d->y, (int)d->ldy, nullptr, 0, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, 0,
+                                         nullptr, L.dxyz, L.partial, L.partial_x, st));
+                CMF_TRY(cmf_colsum(tiles128(M), 3 * O1 + 4, L.partial_x, L.fwd_sums, 0, nullptr, nullptr, st));
+                CMF_TRY(fold(d, L, 0, st));
+            }
+            CMF_TRY(cmf_group_prep(d->B, d->N, d->N, d->S, O1, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, gather_rows(L), L.dxyz,
+                                   gather_wx3(L, M), st));
+            CMF_TRY(cmf_gemm_gather_affine((int)M, C2, O1, d->y, d->ldy, gather_rows(L), L.dxyz, gather_wx3(L, M), b0.a, b0.c, d->w[0], O1,
+                                           L.z2, C2, d->training ? L.partial : nullptr, st));
+        } else {
+            CMF_TRY(cmf_group_affine(d->B, d->N, d->N, d->S, O1, d->y, (int)d->ldy, nullptr, 0, d->xyz, d->xyz, d->wx, (int)d->ldwx, L.idx, 0,
+                                     L.z1, L.dxyz, d->training ? L.partial : nullptr, d->training ? L.partial_x : nullptr, st));
+            if (d->training) CMF_TRY(cmf_colsum(tiles128(M), 3 * O1 + 4, L.partial_x, L.fwd_sums, 0, nullptr, nullptr, st));
+            CMF_TRY(fold(d, L, 0, st));
+            CMF_TRY(fwd_gemm(fwd_layer(d, L, 1), st));
+        }
+        CMF_TRY(fold(d, L, 1, st));
+        CMF_TRY(fwd_gemm(fwd_layer(d, L, 2), st));
+        CMF_TRY(fold(d, L, 2, st));
+        CMF_TRY(cmf_bn_relu_maxpool_sel(P, d->S, C3, L.z3, b2.a, b2.c, L.x, C3, L.argmax, L.zsel, st));
     }
-    CMF_TRY(fold(d, L, 1, M, st));
-    CMF_TRY(fwd_gemm(d, L, M, C2, C3, L.z2, 1, d->w[1], L.z3, st));
-    CMF_TRY(fold(d, L, 2, M, st));
-    CMF_TRY(cmf_bn_relu_maxpool_sel(P, d->S, C3, L.z3, L.bn[2] + 2 * C3, L.bn[2] + 3 * C3, L.x, C3, L.argmax, L.zsel, st));
-    if (part == 1) return 0;
-    // timing diagnostic (results are garbage): the per-point tail left out -- an upper bound for what fusing it can save
-    CMF_TRY(fwd_gemm(d, L, P, C3, C4, L.x, -1, d->w[2], L.z4, st));
-    CMF_TRY(fold(d, L, 3, P, st));
-    CMF_TRY(fwd_gemm(d, L, P, C4, C5, L.z4, 3, d->w[3], L.z5, st));
-    CMF_TRY(fold(d, L, 4, P, st));
-    CMF_TRY(fwd_gemm(d, L, P, C5, C6, L.z5, 4, d->w[4], L.z6, st));
-    CMF_TRY(fold(d, L, 5, P, st));
-    return cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, st);
+    return part == 1 ? 0 : forward_tail(d, L, st);
 }
 
 extern "C" int cmf_setconv_forward(const cmf_setconv_desc *d, void *st) { return setconv_forward_part(d, st, 0); }
@@ -559,8 +637,7 @@ extern "C" int cmf_setconv_queries_counted(int n, const cmf_setconv_desc *descs,
 // sequence below -- the same kernels in the same order as cmf_setconv_forward / _backward, so results are bit-identical.
 static bool tail_batchable(int n, const cmf_setconv_desc *descs)
 {
-    static const bool on = !(getenv("CMF_TAIL_BATCH") && getenv("CMF_TAIL_BATCH")[0] == '0');
-    if (!on || n < 1 || n > CMF_MAX_BATCH) return false;
+    if (!tail_batch_on() || n < 1 || n > CMF_MAX_BATCH) return false;
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
         for (int k = 1; k < 5; ++k)
@@ -577,52 +654,23 @@ extern "C" int cmf_setconv_tail_forward(int n, const cmf_setconv_desc *descs, vo
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (!tail_batchable(n, descs)) {                    // one block after the other, unbatched kernels
-        for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc *d = &descs[i];
-            const Layout L = make_layout(d, d->saved, d->scratch, false);
-            const long long P = (long long)d->B * d->N;
-            const int C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
-            CMF_TRY(fwd_gemm(d, L, P, C3, C4, L.x, -1, d->w[2], L.z4, stream));
-            CMF_TRY(fold(d, L, 3, P, stream));
-            CMF_TRY(fwd_gemm(d, L, P, C4, C5, L.z4, 3, d->w[3], L.z5, stream));
-            CMF_TRY(fold(d, L, 4, P, stream));
-            CMF_TRY(fwd_gemm(d, L, P, C5, C6, L.z5, 4, d->w[4], L.z6, stream));
-            CMF_TRY(fold(d, L, 5, P, stream));
-            CMF_TRY(cmf_affine_relu(P, C6, L.z6, C6, L.bn[5] + 2 * C6, L.bn[5] + 3 * C6, d->out, d->ldo, stream));
-        }
+        for (int i = 0; i < n; ++i) CMF_TRY(forward_tail(&descs[i], make_layout(&descs[i], descs[i].saved, descs[i].scratch, false), stream));
         return 0;
     }
     Layout L[CMF_MAX_BATCH];
     for (int i = 0; i < n; ++i) L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, false);
-    const bool training = descs[0].training != 0;
-    for (int layer = 0; layer < 3; ++layer) {                        // BN layer 3 + layer: (x | z4 | z5) -> (z4 | z5 | z6)
+    for (int l = 3; l < 6; ++l) {
         GemmArgs g[CMF_MAX_BATCH];
         CmfBnFinArgs f[CMF_MAX_BATCH];
         for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc &d = descs[i];
-            const long long P = (long long)d.B * d.N;
-            const int cin = d.C[1 + layer], cout = d.C[2 + layer], lb = 3 + layer;
-            const float *zin = layer == 0 ? L[i].x : (layer == 1 ? L[i].z4 : L[i].z5);
-            float *zout = layer == 0 ? L[i].z4 : (layer == 1 ? L[i].z5 : L[i].z6);
-            GemmArgs &q = g[i];
-            q = GemmArgs{};
-            q.M = (int)P; q.N = cout; q.K = cin; q.A = zin; q.lda = cin; q.B = d.w[2 + layer]; q.ldb = cin; q.C = zout; q.ldc = cout;
-            if (layer > 0) { q.pro_a = L[i].bn[lb - 1] + 2 * cin; q.pro_c = L[i].bn[lb - 1] + 3 * cin; }
-            q.stats = training ? L[i].partial : nullptr;
-            q.split_k = 1;
-            float *b = L[i].bn[lb];
-            f[i] = CmfBnFinArgs{tiles128(P), cout, (double)P, L[i].partial, d.gamma[lb], d.beta[lb], d.eps[lb], d.momentum[lb], d.rmean[lb],
-                                d.rvar[lb], b, b + cout, b + 2 * cout, b + 3 * cout, d.nbt[lb]};
+            g[i] = fwd_layer(&descs[i], L[i], l);
+            f[i] = fold_args(&descs[i], L[i], l);
         }
         CMF_TRY(cmf_thin_fwd_batch(n, g, st));
-        if (training) CMF_TRY(cmf_bn_finalize_batch(n, f, st));
+        if (descs[0].training) CMF_TRY(cmf_bn_finalize_batch(n, f, st));
     }
     CmfAffineArgs a[CMF_MAX_BATCH];
-    for (int i = 0; i < n; ++i) {
-        const cmf_setconv_desc &d = descs[i];
-        const int C6 = d.C[4];
-        a[i] = CmfAffineArgs{(long long)d.B * d.N, C6, L[i].z6, C6, L[i].bn[5] + 2 * C6, L[i].bn[5] + 3 * C6, d.out, d.ldo};
-    }
+    for (int i = 0; i < n; ++i) a[i] = out_args(&descs[i], L[i]);
     return cmf_affine_relu_batch(n, a, st);
 }
 
@@ -634,59 +682,28 @@ extern "C" int cmf_setconv_tail_backward(int n, const cmf_setconv_desc *descs, v
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (!tail_batchable(n, descs)) {
-        for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc *d = &descs[i];
-            const Layout L = make_layout(d, d->saved, d->scratch, true, d->dy != nullptr);
-            const long long P = (long long)d->B * d->N;
-            const int C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
-            const float *b5 = L.bn[5];
-            CMF_TRY(cmf_act_bwd_stats(P, C6, d->dout, d->lddout, L.z6, C6, b5 + 2 * C6, b5 + 3 * C6, b5, b5 + C6, L.t6, L.partial, stream));
-            CMF_TRY(bwd_layer(d, L, 5, P, C6, C5, L.t6, L.z6, d->w[4], L.z5, 4, L.t5, nullptr, d->dw[4], d->acc_w[4], stream));
-            CMF_TRY(bwd_layer(d, L, 4, P, C5, C4, L.t5, L.z5, d->w[3], L.z4, 3, L.t4, nullptr, d->dw[3], d->acc_w[3], stream));
-            CMF_TRY(bwd_layer(d, L, 3, P, C4, C3, L.t4, L.z4, d->w[2], L.x, -1, L.dx, nullptr, d->dw[2], d->acc_w[2], stream));
-        }
+        for (int i = 0; i < n; ++i)
+            CMF_TRY(backward_tail(&descs[i], make_layout(&descs[i], descs[i].saved, descs[i].scratch, true, descs[i].dy != nullptr), stream));
         return 0;
     }
     Layout L[CMF_MAX_BATCH];
     for (int i = 0; i < n; ++i) L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true, descs[i].dy != nullptr);
-    const bool training = descs[0].training != 0;
     {
         CmfActBwdArgs a[CMF_MAX_BATCH];
-        for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc &d = descs[i];
-            const int C6 = d.C[4];
-            const float *b5 = L[i].bn[5];
-            a[i] = CmfActBwdArgs{(long long)d.B * d.N, C6, d.dout, d.lddout, L[i].z6, C6, b5 + 2 * C6, b5 + 3 * C6, b5, b5 + C6, L[i].t6, L[i].partial};
-        }
+        for (int i = 0; i < n; ++i) a[i] = dout_args(&descs[i], L[i]);
         CMF_TRY(cmf_act_bwd_stats_batch(n, a, st));
     }
-    for (int layer = 2; layer >= 0; --layer) {                       // BN layer 3 + layer, weights w[2 + layer]: cout <- cin
+    for (int l = 5; l >= 3; --l) {
         CmfColsumArgs cs[CMF_MAX_BATCH];
         CmfThinBwdCall tb[CMF_MAX_BATCH];
         CmfSplitkArgs sk[CMF_MAX_BATCH];
         for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc &d = descs[i];
-            const long long P = (long long)d.B * d.N;
-            const int cin = d.C[1 + layer], cout = d.C[2 + layer], lb = 3 + layer;
-            float *dU = layer == 2 ? L[i].t6 : (layer == 1 ? L[i].t5 : L[i].t4);
-            const float *zout = layer == 2 ? L[i].z6 : (layer == 1 ? L[i].z5 : L[i].z4);
-            const float *x = layer == 2 ? L[i].z5 : (layer == 1 ? L[i].z4 : L[i].x);
-            float *dUin = layer == 2 ? L[i].t5 : (layer == 1 ? L[i].t4 : L[i].dx);
-            const float *b = L[i].bn[lb], *bi = layer > 0 ? L[i].bn[lb - 1] : nullptr;
-            cs[i] = CmfColsumArgs{tiles128(P), 2 * cout, L[i].partial, L[i].sums, cout, d.dbeta[lb], d.dgamma[lb], d.acc_bn[lb] ? 0 : 1};
-            CmfThinBwdCall &q = tb[i];
-            q = CmfThinBwdCall{};
-            q.rows = P; q.cout = cout; q.cin = cin; q.dU = dU; q.lddu = cout; q.z = zout; q.ldz = cout;
-            q.a = b + 2 * cout; q.mean = b; q.invstd = b + cout; q.sums = training ? L[i].sums : nullptr;
-            q.w = d.w[2 + layer]; q.ldw = cin; q.x = x; q.ldx = cin; q.in_mode = layer > 0 ? 1 : 0;
-            if (bi) { q.a_in = bi + 2 * cin; q.c_in = bi + 3 * cin; q.mean_in = bi; q.invstd_in = bi + cin; }
-            q.dx = dUin; q.lddx = cin; q.stats = layer > 0 ? L[i].partial : nullptr;
-            q.dw = d.dw[2 + layer]; q.lddw = cin; q.accumulate = d.acc_w[2 + layer]; q.slabs = L[i].splitk;
+            tb[i] = bwd_layer_args(&descs[i], L[i], l);
+            cs[i] = bn_grad_args(&descs[i], L[i], l, tiles128(tb[i].rows));
         }
         CMF_TRY(cmf_colsum_batch(n, cs, st));
         CMF_TRY(cmf_thin_bwd_layer_batch(n, tb, st));
-        for (int i = 0; i < n; ++i)
-            sk[i] = CmfSplitkArgs{tb[i].cout, tb[i].cin, tb[i].nslab, tb[i].slabs, tb[i].dw, tb[i].lddw, tb[i].accumulate};
+        for (int i = 0; i < n; ++i) sk[i] = splitk_args(tb[i]);
         CMF_TRY(cmf_splitk_reduce_batch(n, sk, st));
     }
     return 0;
@@ -699,91 +716,69 @@ static int setconv_backward_part(const cmf_setconv_desc *d, void *st, int part)
     CMF_CHECK_ARG(!gather_layout(d) || (d->y && gather_operands_aligned(d)));
     const Layout L = make_layout(d, d->saved, d->scratch, true, d->dy != nullptr);
     const long long P = (long long)d->B * d->N, M = P * d->S;
-    const int O1 = d->O1, C2 = d->C[0], C3 = d->C[1], C4 = d->C[2], C5 = d->C[3], C6 = d->C[4];
-    const float *b5 = L.bn[5], *b2 = L.bn[2];
+    const int O1 = d->O1, C2 = d->C[0], C3 = d->C[1];
+    const Bn &b0 = L.bn[0];
+    const bool chain = chain_train(d);
+    const int wv = chain ? (int)cmf_setconv_chain_waves(M, 1) : 0;          // statistics rows of a chain pass
     // The inverse index of the grouping is only needed by the scatter at the very end, but its kernel wants most of a
     // CU's LDS (one workgroup per sample, 132 KB at N = 256): issued there it has to wait until a CU has drained the
     // GEMM workgroups of the other chains -- up to a tile's duration on the critical tail of the chain.  Issued first
     // it runs next to the small per-point kernels and is long done when the scatter needs it.
     if (d->dy) CMF_TRY(cmf_build_inverse_ps(d->B, d->N, d->N, d->S, L.idx, L.offsets, L.inv, st));
-    // layer 6 .. 4 (per point)
-    if (part != 2) {
-    CMF_TRY(cmf_act_bwd_stats(P, C6, d->dout, d->lddout, L.z6, C6, b5 + 2 * C6, b5 + 3 * C6, b5, b5 + C6, L.t6, L.partial, st));
-    CMF_TRY(bwd_layer(d, L, 5, P, C6, C5, L.t6, L.z6, d->w[4], L.z5, 4, L.t5, nullptr, d->dw[4], d->acc_w[4], st));
-    CMF_TRY(bwd_layer(d, L, 4, P, C5, C4, L.t5, L.z5, d->w[3], L.z4, 3, L.t4, nullptr, d->dw[3], d->acc_w[3], st));
-    CMF_TRY(bwd_layer(d, L, 3, P, C4, C3, L.t4, L.z4, d->w[2], L.x, -1, L.dx, nullptr, d->dw[2], d->acc_w[2], st));
-    }
-    // max over the ball, layers 3 .. 1 (per neighbour slot)
-    static const bool fused = !(getenv("CMF_THIN_FUSED") && getenv("CMF_THIN_FUSED")[0] == '0');
-    // the wide-input form of the fused layer (64 <- 256 channels, second encoder): CMF_THIN_WIDE=0 keeps max-pool backward, BN
-    // backward and the two tiled GEMMs (A/B: 22.6 vs 22.9 ms per step)
-    static const bool wide = !(getenv("CMF_THIN_WIDE") && getenv("CMF_THIN_WIDE")[0] == '0');
-    if (chain_train(d)) {
-        // the chain's backward: the pooled gradient per point with layer 3's BN-backward sums from the selected pre-activations, then two
-        // passes that recompute the layers they differentiate (weight-gradient slabs per workgroup, statistics rows per wave)
-        float *g = L.dU3;
-        const int wv = (int)cmf_setconv_chain_waves(M, 1), nslab = wv / 4;
-        CMF_TRY(cmf_maxpool_bwd_point_sel(P, C3, L.dx, C3, L.z3, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, g, L.partial, st));
-        if (d->acc_bn[2]) CMF_TRY(cmf_colsum_finalize(tiles128(P), C3, L.partial, L.sums, d->dbeta[2], d->dgamma[2], st));
-        else CMF_TRY(cmf_colsum_store(tiles128(P), 2 * C3, L.partial, L.sums, C3, d->dbeta[2], d->dgamma[2], st));
-        CMF_TRY(cmf_setconv_chain_pass(2, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
+    if (part != 2) CMF_TRY(backward_tail(d, L, st));                         // l = 5 .. 3 (per point)
+    // max over the ball, l = 2 .. 1 (per neighbour slot).  Where a fused kernel takes l = 2, the gradient of the pooled tensor is
+    // kept per POINT (g, in L.dx's neighbour L.dU3) and expanded on the fly -- the [M, C3] matrix is neither written nor read.
+    float *g = L.dU3;
+    const CmfThinBwdCall q = bwd_layer_args(d, L, 2);
+    const bool fused = thin_fused_on() && M % 128 == 0 && d->dw[1];
+    if (chain) {
+        // the chain's backward: the pooled gradient with the BN-backward sums of l = 2 from the selected pre-activations (kept in z3's slot),
+        // then two passes that recompute the layers they differentiate (weight-gradient slabs per workgroup, statistics rows per wave)
+        const float *bn0 = L.bn[0].block(), *bn1 = L.bn[1].block(), *bn2 = L.bn[2].block();
+        const int nslab = wv / 4;
+        CMF_TRY(pooled_grad_head(d, L, L.z3, st));
+        CMF_TRY(cmf_setconv_chain_pass(2, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, bn0, bn1, bn2, d->w[0], d->w[1],
                                        nullptr, 0, nullptr, L.argmax, L.partial, g, nullptr, L.dU2, L.splitk, st));
         if (d->dw[1]) CMF_TRY(cmf_splitk_reduce(C3, C2, nslab, L.splitk, d->dw[1], C2, d->acc_w[1], (hipStream_t)st));
-        if (d->acc_bn[1]) CMF_TRY(cmf_colsum_finalize(wv, C2, L.partial, L.sums, d->dbeta[1], d->dgamma[1], st));
-        else CMF_TRY(cmf_colsum_store(wv, 2 * C2, L.partial, L.sums, C2, d->dbeta[1], d->dgamma[1], st));
-        CMF_TRY(cmf_setconv_chain_pass(3, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0], L.bn[1], L.bn[2], d->w[0], d->w[1],
+        CMF_TRY(bn_grad_sums(bn_grad_args(d, L, 1, wv), st));
+        CMF_TRY(cmf_setconv_chain_pass(3, M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, bn0, bn1, bn2, d->w[0], d->w[1],
                                        nullptr, 0, nullptr, nullptr, L.partial, nullptr, L.dU2, L.dU1, L.splitk, st));
         if (d->dw[0]) CMF_TRY(cmf_splitk_reduce(C2, O1, nslab, L.splitk, d->dw[0], O1, d->acc_w[0], (hipStream_t)st));
-    } else
-    if (fused && cmf_thin_bwd_supported(C3, C2) && M % 128 == 0 && C3 % 32 == 0 && C2 % 32 == 0 && d->dw[1]) {
-        // narrow layers: the gradient of the pooled tensor is kept per POINT (g, in L.dx's neighbour L.dU3) and expanded
-        // by the fused layer kernel on the fly -- the [M, C3] matrix is neither written nor read
-        float *g = L.dU3;
-        CMF_TRY(cmf_maxpool_bwd_point_sel(P, C3, L.dx, C3, L.zsel, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, g, L.partial, st));
-        if (d->acc_bn[2]) CMF_TRY(cmf_colsum_finalize(tiles128(P), C3, L.partial, L.sums, d->dbeta[2], d->dgamma[2], st));
-        else CMF_TRY(cmf_colsum_store(tiles128(P), 2 * C3, L.partial, L.sums, C3, d->dbeta[2], d->dgamma[2], st));
-        const float *b1 = L.bn[1];
-        CMF_TRY(cmf_thin_bwd_layer_pooled(P, d->S, C3, C2, g, L.argmax, L.z3, b2 + 2 * C3, b2, b2 + C3, d->training ? L.sums : nullptr,
-                                          d->w[1], L.z2, b1 + 2 * C2, b1 + 3 * C2, b1, b1 + C2, L.dU2, L.partial, d->dw[1], d->acc_w[1],
-                                          L.splitk, st));
-    } else if (fused && wide && cmf_thin_bwd_wide_supported(C3, C2) && M % 128 == 0 && d->dw[1]) {
-        // 64 <- 256 channels (second encoder): the same single pass, a workgroup per (row range, 128 input channels)
-        float *g = L.dU3;
-        CMF_TRY(cmf_maxpool_bwd_point_sel(P, C3, L.dx, C3, L.zsel, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, g, L.partial, st));
-        if (d->acc_bn[2]) CMF_TRY(cmf_colsum_finalize(tiles128(P), C3, L.partial, L.sums, d->dbeta[2], d->dgamma[2], st));
-        else CMF_TRY(cmf_colsum_store(tiles128(P), 2 * C3, L.partial, L.sums, C3, d->dbeta[2], d->dgamma[2], st));
-        const float *b1 = L.bn[1];
-        CMF_TRY(cmf_thin_bwd_wide_layer(M, C2, nullptr, C3, g, L.argmax, d->S, L.z3, C3, b2 + 2 * C3, b2, b2 + C3,
-                                        d->training ? L.sums : nullptr, d->w[1], C2, L.z2, C2, b1 + 2 * C2, b1 + 3 * C2, b1, b1 + C2,
-                                        L.dU2, C2, L.partial, d->dw[1], C2, d->acc_w[1], L.splitk, st));
     } else {
-        CMF_TRY(cmf_maxpool_bwd(P, d->S, C3, L.dx, C3, L.z3, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, L.argmax, L.dU3, L.partial, st));
-        CMF_TRY(bwd_layer(d, L, 2, M, C3, C2, L.dU3, L.z3, d->w[1], L.z2, 1, L.dU2, nullptr, d->dw[1], d->acc_w[1], st));
+        if (fused && cmf_thin_bwd_supported(C3, C2) && C3 % 32 == 0 && C2 % 32 == 0) {                  // narrow layers
+            CMF_TRY(pooled_grad_head(d, L, L.zsel, st));
+            CMF_TRY(cmf_thin_bwd_layer_pooled(P, d->S, q.cout, q.cin, g, L.argmax, q.z, q.a, q.mean, q.invstd, q.sums, q.w, q.x, q.a_in, q.c_in,
+                                              q.mean_in, q.invstd_in, q.dx, q.stats, q.dw, q.accumulate, q.slabs, st));
+        } else if (fused && thin_wide_on() && cmf_thin_bwd_wide_supported(C3, C2)) {
+            // 64 <- 256 channels (second encoder): the same single pass, a workgroup per (row range, 128 input channels).  CMF_THIN_WIDE=0
+            // keeps max-pool backward, BN backward and the two tiled GEMMs (A/B: 22.6 vs 22.9 ms per step)
+            CMF_TRY(pooled_grad_head(d, L, L.zsel, st));
+            CMF_TRY(cmf_thin_bwd_wide_layer(q.rows, q.cin, nullptr, q.lddu, g, L.argmax, d->S, q.z, q.ldz, q.a, q.mean, q.invstd, q.sums, q.w, q.ldw,
+                                            q.x, q.ldx, q.a_in, q.c_in, q.mean_in, q.invstd_in, q.dx, q.lddx, q.stats, q.dw, q.lddw, q.accumulate,
+                                            q.slabs, st));
+        } else {
+            const Bn &b2 = L.bn[2];
+            CMF_TRY(cmf_maxpool_bwd(P, d->S, C3, L.dx, C3, L.z3, b2.a, b2.c, b2.mean, b2.invstd, L.argmax, L.dU3, L.partial, st));
+            CMF_TRY(bwd_layer(d, L, 2, st));
+        }
+        CMF_TRY(gather_layout(d) ? bwd_layer1_gather(d, L, st) : bwd_layer(d, L, 1, st));
     }
-    const bool chain = chain_train(d);
-    if (chain) {}
-    else if (train_gather(d)) CMF_TRY(bwd_layer1_gather(d, L, M, C2, O1, st));
-    else
-    CMF_TRY(bwd_layer(d, L, 1, M, C2, O1, L.dU2, L.z2, d->w[0], L.z1, 0, L.dU1, L.dxyz, d->dw[0], d->acc_w[0], st));
     // first layer: sums {s1,s2,q0,q1,q2}; dgamma/dbeta; dW_xyz from sums; BN backward folded into the scatter
-    const float *b0 = L.bn[0];
-    const int rows0 = chain ? (int)cmf_setconv_chain_waves(M, 1) : tiles128(M);      // statistics rows of the pass that formed dU1
-    if (d->acc_bn[0]) CMF_TRY(cmf_colsum(rows0, 5 * O1, L.partial, L.sums, O1, d->dbeta[0], d->dgamma[0], st));
-    else CMF_TRY(cmf_colsum_store(rows0, 5 * O1, L.partial, L.sums, O1, d->dbeta[0], d->dgamma[0], st));
+    CMF_TRY(bn_grad_sums(bn_grad_args(d, L, 0, chain ? wv : tiles128(M)), st));       // (the statistics rows of the pass that formed dU1)
+    const float *sums = d->training ? L.sums : nullptr;
+    const float inv_count = (float)(1.0 / (double)M);
     if (d->dwx)
-        CMF_TRY(cmf_setconv_dwx(O1, (float)(1.0 / (double)M), d->training, L.sums, L.fwd_sums, b0 + 2 * O1, b0, b0 + O1, d->dwx,
-                                (int)d->lddwx, d->acc_wx, st));
+        CMF_TRY(cmf_setconv_dwx(O1, inv_count, d->training, L.sums, L.fwd_sums, b0.a, b0.mean, b0.invstd, d->dwx, (int)d->lddwx, d->acc_wx, st));
     if (d->dy) {
         // z1 rows of one source point differ only by wx . dxyz: the BN-backward part of the scatter has a closed form,
-        // so only dU1 is streamed (csrc/group_rows.hip)
-        if (train_gather_sum(d))
+        // so only dU1 (or its pieces, summed inside the GEMM) is streamed (csrc/group_rows.hip)
+        const int lddy = d->lddy ? (int)d->lddy : O1;
+        if (gather_sum_layout(d))
             CMF_TRY(cmf_group_rows_grad_bn_cf_pieces(d->B, d->N, O1, d->N * d->S, d->S, sum_slots(d, L).pieces, d->y, d->ldy, d->wx, d->ldwx, d->xyz,
-                                                     d->xyz, b0 + 2 * O1, b0, b0 + O1, d->training ? L.sums : nullptr, (float)(1.0 / (double)M), L.offsets, L.inv, d->dy,
-                                                     d->lddy ? (int)d->lddy : O1, st));
+                                                     d->xyz, b0.a, b0.mean, b0.invstd, sums, inv_count, L.offsets, L.inv, d->dy, lddy, st));
         else
-        CMF_TRY(cmf_group_rows_grad_bn_cf(d->B, d->N, O1, d->N * d->S, d->S, L.dU1, d->y, d->ldy, d->wx, d->ldwx, d->xyz, d->xyz,
-                                          b0 + 2 * O1, b0, b0 + O1, d->training ? L.sums : nullptr, (float)(1.0 / (double)M),
-                                          L.offsets, L.inv, d->dy, d->lddy ? (int)d->lddy : O1, st));
+            CMF_TRY(cmf_group_rows_grad_bn_cf(d->B, d->N, O1, d->N * d->S, d->S, L.dU1, d->y, d->ldy, d->wx, d->ldwx, d->xyz, d->xyz, b0.a, b0.mean,
+                                              b0.invstd, sums, inv_count, L.offsets, L.inv, d->dy, lddy, st));
     }
     return 0;
 }
@@ -796,12 +791,6 @@ extern "C" int cmf_setconv_backward(const cmf_setconv_desc *d, void *st) { retur
 // as they take to enqueue, so one host thread cannot keep four streams fed.  Stream ordering against the
 // caller's stream is the caller's business (events before / after the call); nothing is synchronised here.
 // ---------------------------------------------------------------------------------------------------------------
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
-#include <vector>
-
 namespace {
 // Persistent host threads for the chains of a multi-scale call: a chain is ~20 / ~45 launches, i.e. a few hundred
 // microseconds of enqueueing -- creating and joining a std::thread per chain and call (up to 7 spawns, ~6 calls per step)
@@ -896,12 +885,11 @@ static int setconv_multi(int n, const cmf_setconv_desc *descs, void *const *stre
 // ---------------------------------------------------------------------------------------------------------------
 static bool body_batchable(int n, const cmf_setconv_desc *descs)
 {
-    static const bool on = !(getenv("CMF_BODY_BATCH") && getenv("CMF_BODY_BATCH")[0] == '0');
-    if (!on || n < 2 || n > CMF_MAX_BATCH) return false;
+    if (!body_batch_on() || n < 2 || n > CMF_MAX_BATCH) return false;
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
         const long long M = (long long)d.B * d.N * d.S;
-        if (!d.training || d.inference || !d.idx_ready || train_gather(&d)) return false;
+        if (!d.training || d.inference || !d.idx_ready || gather_layout(&d)) return false;
         if (d.O1 != descs[0].O1 || d.C[0] != descs[0].C[0] || d.C[1] != descs[0].C[1]) return false;
         if (d.O1 > 64 || d.O1 % 32 || d.C[0] > 64 || d.C[0] % 32 || d.C[1] > 64 || d.C[1] % 32) return false;
         if (M % 128 || M >= (1ll << 31) || d.ldy % 4 || ((uintptr_t)d.y & 15)) return false;
@@ -912,8 +900,7 @@ static bool body_batchable(int n, const cmf_setconv_desc *descs)
 // inference of the narrow blocks (eval-mode BN, no backward call to follow): their register-chain kernels as ONE launch
 static bool infer_batchable(int n, const cmf_setconv_desc *descs)
 {
-    static const bool on = !(getenv("CMF_BODY_BATCH") && getenv("CMF_BODY_BATCH")[0] == '0');
-    if (!on || n < 2 || n > CMF_MAX_BATCH) return false;
+    if (!body_batch_on() || n < 2 || n > CMF_MAX_BATCH) return false;
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
         const long long M = (long long)d.B * d.N * d.S;
@@ -932,13 +919,9 @@ static int setconv_infer_bodies_batch(int n, const cmf_setconv_desc *descs, hipS
         const cmf_setconv_desc &d = descs[i];
         CMF_CHECK_ARG(d.xyz && d.y && d.wx && d.saved && d.scratch && d.out);
         const Layout L = make_layout(&d, d.saved, d.scratch, false);
-        FoldAll &f = fb.a[i];
-        for (int l = 0; l < 6; ++l) {
-            f.C[l] = chan(&d, l); f.gamma[l] = d.gamma[l]; f.beta[l] = d.beta[l]; f.rmean[l] = d.rmean[l]; f.rvar[l] = d.rvar[l];
-            f.eps[l] = d.eps[l]; f.out[l] = L.bn[l];
-        }
-        q[i] = CmfChainInferArgs{(long long)d.B * d.N * d.S, d.N, d.S, L.idx, d.xyz, d.y, d.ldy, d.wx, d.ldwx, L.bn[0], L.bn[1], L.bn[2], d.w[0], d.w[1],
-                                 L.x, d.C[1]};
+        fb.a[i] = fold_all_args(&d, L);
+        q[i] = CmfChainInferArgs{(long long)d.B * d.N * d.S, d.N, d.S, L.idx, d.xyz, d.y, d.ldy, d.wx, d.ldwx, L.bn[0].block(), L.bn[1].block(),
+                                 L.bn[2].block(), d.w[0], d.w[1], L.x, d.C[1]};
     }
     hipLaunchKernelGGL(bn_fold_eval_batch_kernel, dim3(6, n), dim3(256), 0, st, fb);
     CMF_TRY(cmf_launch_status());
@@ -964,7 +947,7 @@ static int setconv_forward_bodies_batch(int n, const cmf_setconv_desc *descs_in,
         CMF_CHECK_ARG(descs[i].xyz && descs[i].y && descs[i].wx && descs[i].saved && descs[i].scratch && descs[i].out);
         L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, false);
     }
-    const int O1 = descs[0].O1, C2 = descs[0].C[0], C3 = descs[0].C[1];
+    const int O1 = descs[0].O1, C3 = descs[0].C[1];
     {   // z1 = y[idx] + Wx . dxyz with its statistics; the z * d_k sums for dW_xyz
         CmfGroupAffineArgs ga[CMF_MAX_BATCH];
         CmfColsumArgs cs[CMF_MAX_BATCH];
@@ -978,27 +961,19 @@ static int setconv_forward_bodies_batch(int n, const cmf_setconv_desc *descs_in,
         CMF_TRY(cmf_group_affine_batch(n, ga, st));
         CMF_TRY(cmf_colsum_batch(n, cs, st));
     }
-    for (int layer = 0; layer < 3; ++layer) {            // fold BN layer `layer`, then (layers 0, 1) the next 1x1 conv / (layer 2) the max over the ball
+    for (int l = 0; l < 3; ++l) {                        // fold BN layer l, then (l = 0, 1) the next 1x1 conv / (l = 2) the max over the ball
         CmfBnFinArgs f[CMF_MAX_BATCH];
         GemmArgs g[CMF_MAX_BATCH];
         CmfPoolArgs pl[CMF_MAX_BATCH];
-        const int C = layer == 0 ? O1 : (layer == 1 ? C2 : C3), cout = layer == 0 ? C2 : C3;
         for (int i = 0; i < n; ++i) {
             const cmf_setconv_desc &d = descs[i];
-            const long long P = (long long)d.B * d.N, M = P * d.S;
-            float *b = L[i].bn[layer];
-            f[i] = CmfBnFinArgs{tiles128(M), C, (double)M, L[i].partial, d.gamma[layer], d.beta[layer], d.eps[layer], d.momentum[layer],
-                                d.rmean[layer], d.rvar[layer], b, b + C, b + 2 * C, b + 3 * C, d.nbt[layer]};
-            if (layer < 2) {
-                GemmArgs &q = g[i];
-                q = GemmArgs{};
-                q.M = (int)M; q.N = cout; q.K = C; q.A = layer == 0 ? L[i].z1 : L[i].z2; q.lda = C; q.B = d.w[layer]; q.ldb = C;
-                q.C = layer == 0 ? L[i].z2 : L[i].z3; q.ldc = cout; q.pro_a = b + 2 * C; q.pro_c = b + 3 * C; q.stats = L[i].partial; q.split_k = 1;
-            } else
-                pl[i] = CmfPoolArgs{P, d.S, C3, L[i].z3, b + 2 * C3, b + 3 * C3, L[i].x, C3, L[i].argmax, 0, L[i].zsel};
+            const Bn &b = L[i].bn[l];
+            f[i] = fold_args(&d, L[i], l);
+            if (l < 2) g[i] = fwd_layer(&d, L[i], l + 1);
+            else pl[i] = CmfPoolArgs{(long long)d.B * d.N, d.S, C3, L[i].z3, b.a, b.c, L[i].x, C3, L[i].argmax, 0, L[i].zsel};
         }
         CMF_TRY(cmf_bn_finalize_batch(n, f, st));
-        if (layer < 2) CMF_TRY(cmf_thin_fwd_batch(n, g, st));
+        if (l < 2) CMF_TRY(cmf_thin_fwd_batch(n, g, st));
         else CMF_TRY(cmf_bn_relu_maxpool_batch(n, pl, st));
     }
     return 0;
@@ -1009,10 +984,9 @@ static int setconv_forward_bodies_batch(int n, const cmf_setconv_desc *descs_in,
 static bool body_batchable_bwd(int n, const cmf_setconv_desc *descs)
 {
     if (!body_batchable(n, descs)) return false;
-    static const bool fused = !(getenv("CMF_THIN_FUSED") && getenv("CMF_THIN_FUSED")[0] == '0');
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
-        if (!fused || !d.dw[0] || !d.dw[1] || !d.dout || !cmf_thin_bwd_supported(d.C[1], d.C[0]) || !cmf_thin_bwd_supported(d.C[0], d.O1)) return false;
+        if (!thin_fused_on() || !d.dw[0] || !d.dw[1] || !d.dout || !cmf_thin_bwd_supported(d.C[1], d.C[0]) || !cmf_thin_bwd_supported(d.C[0], d.O1)) return false;
         if (d.C[1] != 64 || d.C[0] != 32 || d.O1 != 32) return false;                 // the batched instantiations of the fused layer
         if ((d.dy != nullptr) != (descs[0].dy != nullptr) || (d.dwx != nullptr) != (descs[0].dwx != nullptr)) return false;
         if (d.B != descs[0].B || d.N != descs[0].N || d.N > 256 || d.S > 64) return false;
@@ -1037,7 +1011,7 @@ static int setconv_backward_bodies_batch(int n, const cmf_setconv_desc *descs_in
         CMF_CHECK_ARG(descs[i].xyz && descs[i].saved && descs[i].scratch && descs[i].dout);
         L[i] = make_layout(&descs[i], descs[i].saved, descs[i].scratch, true, descs[i].dy != nullptr);
     }
-    const int O1 = descs[0].O1, C2 = descs[0].C[0], C3 = descs[0].C[1];
+    const int O1 = descs[0].O1, C3 = descs[0].C[1];
     const bool want_dy = descs[0].dy != nullptr, want_dwx = descs[0].dwx != nullptr;
     if (want_dy) {
         CmfInverseArgs iv[CMF_MAX_BATCH];
@@ -1047,47 +1021,26 @@ static int setconv_backward_bodies_batch(int n, const cmf_setconv_desc *descs_in
     CmfColsumArgs cs[CMF_MAX_BATCH];
     CmfThinBwdCall tb[CMF_MAX_BATCH];
     CmfSplitkArgs sk[CMF_MAX_BATCH];
-    {   // max over the ball -> the pooled gradient per point with layer 3's BN-backward sums; layer 3 (64 <- 32) from the pooled gradient
+    for (int l = 2; l >= 1; --l) {
+        // l = 2: max over the ball -> the pooled gradient per point (g) with the layer's BN-backward sums, then the layer (64 <- 32) from
+        // the pooled gradient; l = 1: the layer (32 <- 32) with the dxyz sums of the first layer's coordinate weights
         CmfPoolBwdArgs pb[CMF_MAX_BATCH];
         for (int i = 0; i < n; ++i) {
             const cmf_setconv_desc &d = descs[i];
-            const long long P = (long long)d.B * d.N;
-            const float *b2 = L[i].bn[2], *b1 = L[i].bn[1];
-            float *g = L[i].dU3;
-            pb[i] = CmfPoolBwdArgs{P, d.S, C3, L[i].dx, C3, L[i].zsel, b2 + 2 * C3, b2 + 3 * C3, b2, b2 + C3, L[i].argmax, g, L[i].partial, 1};
-            cs[i] = CmfColsumArgs{tiles128(P), 2 * C3, L[i].partial, L[i].sums, C3, d.dbeta[2], d.dgamma[2], d.acc_bn[2] ? 0 : 1};
             CmfThinBwdCall &q = tb[i];
-            q = CmfThinBwdCall{};
-            q.rows = P * d.S; q.cout = C3; q.cin = C2; q.dU = nullptr; q.lddu = C3; q.z = L[i].z3; q.ldz = C3;
-            q.a = b2 + 2 * C3; q.mean = b2; q.invstd = b2 + C3; q.sums = L[i].sums;
-            q.w = d.w[1]; q.ldw = C2; q.x = L[i].z2; q.ldx = C2; q.in_mode = 1;
-            q.a_in = b1 + 2 * C2; q.c_in = b1 + 3 * C2; q.mean_in = b1; q.invstd_in = b1 + C2;
-            q.dx = L[i].dU2; q.lddx = C2; q.stats = L[i].partial; q.dw = d.dw[1]; q.lddw = C2; q.accumulate = d.acc_w[1]; q.slabs = L[i].splitk;
-            q.pool_g = g; q.pool_am = L[i].argmax; q.pool_S = d.S;
+            q = bwd_layer_args(&d, L[i], l);
+            cs[i] = bn_grad_args(&d, L[i], l, tiles128(l == 2 ? rows_of(&d, 3) : q.rows));      // (l = 2: partials per point)
+            if (l == 2) {
+                const Bn &b2 = L[i].bn[2];
+                float *g = L[i].dU3;
+                pb[i] = CmfPoolBwdArgs{rows_of(&d, 3), d.S, C3, L[i].dx, C3, L[i].zsel, b2.a, b2.c, b2.mean, b2.invstd, L[i].argmax, g, L[i].partial, 1};
+                q.dU = nullptr; q.pool_g = g; q.pool_am = L[i].argmax; q.pool_S = d.S;
+            }
         }
-        CMF_TRY(cmf_maxpool_bwd_point_batch(n, pb, st));
+        if (l == 2) CMF_TRY(cmf_maxpool_bwd_point_batch(n, pb, st));
         CMF_TRY(cmf_colsum_batch(n, cs, st));
         CMF_TRY(cmf_thin_bwd_layer_batch(n, tb, st));
-        for (int i = 0; i < n; ++i) sk[i] = CmfSplitkArgs{C3, C2, tb[i].nslab, tb[i].slabs, tb[i].dw, tb[i].lddw, tb[i].accumulate};
-        CMF_TRY(splitk_batch_or_each(n, sk, st));
-    }
-    {   // layer 2 (32 <- 32) with the dxyz sums of the first layer's coordinate weights
-        for (int i = 0; i < n; ++i) {
-            const cmf_setconv_desc &d = descs[i];
-            const long long M = (long long)d.B * d.N * d.S;
-            const float *b1 = L[i].bn[1], *b0 = L[i].bn[0];
-            cs[i] = CmfColsumArgs{tiles128(M), 2 * C2, L[i].partial, L[i].sums, C2, d.dbeta[1], d.dgamma[1], d.acc_bn[1] ? 0 : 1};
-            CmfThinBwdCall &q = tb[i];
-            q = CmfThinBwdCall{};
-            q.rows = M; q.cout = C2; q.cin = O1; q.dU = L[i].dU2; q.lddu = C2; q.z = L[i].z2; q.ldz = C2;
-            q.a = b1 + 2 * C2; q.mean = b1; q.invstd = b1 + C2; q.sums = L[i].sums;
-            q.w = d.w[0]; q.ldw = O1; q.x = L[i].z1; q.ldx = O1; q.in_mode = 1;
-            q.a_in = b0 + 2 * O1; q.c_in = b0 + 3 * O1; q.mean_in = b0; q.invstd_in = b0 + O1; q.dxyz = L[i].dxyz;
-            q.dx = L[i].dU1; q.lddx = O1; q.stats = L[i].partial; q.dw = d.dw[0]; q.lddw = O1; q.accumulate = d.acc_w[0]; q.slabs = L[i].splitk;
-        }
-        CMF_TRY(cmf_colsum_batch(n, cs, st));
-        CMF_TRY(cmf_thin_bwd_layer_batch(n, tb, st));
-        for (int i = 0; i < n; ++i) sk[i] = CmfSplitkArgs{C2, O1, tb[i].nslab, tb[i].slabs, tb[i].dw, tb[i].lddw, tb[i].accumulate};
+        for (int i = 0; i < n; ++i) sk[i] = splitk_args(tb[i]);
         CMF_TRY(splitk_batch_or_each(n, sk, st));
     }
     {   // first layer: sums {s1, s2, q0, q1, q2}; dgamma / dbeta; dW_xyz; BN backward folded into the scatter
@@ -1095,12 +1048,13 @@ static int setconv_backward_bodies_batch(int n, const cmf_setconv_desc *descs_in
         CmfScatterArgs sc[CMF_MAX_BATCH];
         for (int i = 0; i < n; ++i) {
             const cmf_setconv_desc &d = descs[i];
-            const long long M = (long long)d.B * d.N * d.S;
-            const float *b0 = L[i].bn[0];
-            cs[i] = CmfColsumArgs{tiles128(M), 5 * O1, L[i].partial, L[i].sums, O1, d.dbeta[0], d.dgamma[0], d.acc_bn[0] ? 0 : 1};
-            dx[i] = CmfDwxArgs{O1, (float)(1.0 / (double)M), d.training, L[i].sums, L[i].fwd_sums, b0 + 2 * O1, b0, b0 + O1, d.dwx, (int)d.lddwx, d.acc_wx};
-            sc[i] = CmfScatterArgs{d.N, d.N * d.S, d.S, L[i].dU1, d.y, d.ldy, d.wx, d.ldwx, d.xyz, d.xyz, b0 + 2 * O1, b0, b0 + O1, L[i].sums,
-                                   (float)(1.0 / (double)M), L[i].offsets, L[i].inv, d.dy, d.lddy ? (int)d.lddy : O1};
+            const long long M = rows_of(&d, 0);
+            const float inv_count = (float)(1.0 / (double)M);
+            const Bn &b0 = L[i].bn[0];
+            cs[i] = bn_grad_args(&d, L[i], 0, tiles128(M));
+            dx[i] = CmfDwxArgs{O1, inv_count, d.training, L[i].sums, L[i].fwd_sums, b0.a, b0.mean, b0.invstd, d.dwx, (int)d.lddwx, d.acc_wx};
+            sc[i] = CmfScatterArgs{d.N, d.N * d.S, d.S, L[i].dU1, d.y, d.ldy, d.wx, d.ldwx, d.xyz, d.xyz, b0.a, b0.mean, b0.invstd, L[i].sums,
+                                   inv_count, L[i].offsets, L[i].inv, d.dy, d.lddy ? (int)d.lddy : O1};
         }
         CMF_TRY(cmf_colsum_batch(n, cs, st));
         if (want_dwx) CMF_TRY(cmf_setconv_dwx_batch(n, dx, st));
@@ -1185,7 +1139,8 @@ extern "C" int cmf_setconv_backward_bodies_multi(int n, const cmf_setconv_desc *
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 struct MlpLayout {
-    float *z[4], *bn[4];
+    float *z[4];
+    Bn bn[4];
     float *partial, *sums, *dU[4], *splitk;
     size_t saved_floats, scratch_floats;
 };
@@ -1194,7 +1149,7 @@ MlpLayout mlp_layout(const cmf_mlp_desc *d, float *saved, float *scratch, bool b
     MlpLayout L;
     Bump s(saved);
     for (int l = 0; l < d->L; ++l) L.z[l] = s.take((size_t)d->M * d->C[l + 1]);
-    for (int l = 0; l < d->L; ++l) L.bn[l] = s.take(4 * (size_t)d->C[l + 1]);
+    for (int l = 0; l < d->L; ++l) L.bn[l] = Bn(s.take(4 * (size_t)d->C[l + 1]), d->C[l + 1]);
     L.saved_floats = s.off;
     Bump t(scratch);
     int cmax = 0;
@@ -1237,21 +1192,14 @@ extern "C" int cmf_mlp_forward(const cmf_mlp_desc *d, void *st)
     const MlpLayout L = mlp_layout(d, d->saved, d->scratch, false);
     for (int l = 0; l < d->L; ++l) {
         const int cin = d->C[l], cout = d->C[l + 1];
-        const float *zin = l == 0 ? d->x : L.z[l - 1];
-        const long long ldin = l == 0 ? d->ldx : cin;
-        const float *pa = l > 0 ? L.bn[l - 1] + 2 * cin : nullptr, *pc = l > 0 ? L.bn[l - 1] + 3 * cin : nullptr;
-        CMF_TRY(cmf_gemm((int)d->M, cout, cin, 0, 1, zin, ldin, d->w[l], cin, L.z[l], cout, pa, pc, nullptr, nullptr, nullptr, 0,
-                         d->training ? L.partial : nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0, st));
-        float *b = L.bn[l];
-        if (d->training)
-            CMF_TRY(cmf_bn_finalize(tiles128(d->M), cout, (double)d->M, L.partial, d->gamma[l], d->beta[l], d->eps[l], d->momentum[l],
-                                    d->rmean[l], d->rvar[l], b, b + cout, b + 2 * cout, b + 3 * cout, d->nbt[l], st));
-        else
-            CMF_TRY(cmf_bn_finalize(0, cout, 1.0, nullptr, d->gamma[l], d->beta[l], d->eps[l], 0.f, d->rmean[l], d->rvar[l], b, b + cout,
-                                    b + 2 * cout, b + 3 * cout, nullptr, st));
+        CMF_TRY(fwd_gemm(fwd_gemm_args(d->M, cin, cout, l == 0 ? d->x : L.z[l - 1], l == 0 ? d->ldx : cin, l > 0 ? L.bn[l - 1] : Bn(), d->w[l],
+                                       L.z[l], d->training ? L.partial : nullptr), st));
+        CmfBnFinArgs f = bn_fin_args(d, l, d->M, cout, L.partial, L.bn[l]);
+        if (!d->training) { f.tiles = 0; f.count = 1.0; f.partial = nullptr; f.momentum = 0.f; f.nbt = nullptr; }      // fold the running statistics
+        CMF_TRY(bn_finalize(f, st));
     }
     const int cl = d->C[d->L];
-    return cmf_affine_relu(d->M, cl, L.z[d->L - 1], cl, L.bn[d->L - 1] + 2 * cl, L.bn[d->L - 1] + 3 * cl, d->out, d->ldo, st);
+    return affine_relu(affine_args(d->M, cl, L.z[d->L - 1], L.bn[d->L - 1], d->out, d->ldo), st);
 }
 
 extern "C" int cmf_mlp_backward(const cmf_mlp_desc *d, void *st)
@@ -1259,32 +1207,19 @@ extern "C" int cmf_mlp_backward(const cmf_mlp_desc *d, void *st)
     CMF_CHECK_ARG(mlp_ok(d) && d->x && d->saved && d->scratch && d->dout && d->lddout % 4 == 0 && (!d->dx || d->lddx % 4 == 0));
     const MlpLayout L = mlp_layout(d, d->saved, d->scratch, true);
     const long long M = d->M;
-    {
-        const int c = d->C[d->L];
-        const float *b = L.bn[d->L - 1];
-        CMF_TRY(cmf_act_bwd_stats(M, c, d->dout, d->lddout, L.z[d->L - 1], c, b + 2 * c, b + 3 * c, b, b + c, L.dU[d->L - 1], L.partial, st));
-    }
-    for (int l = d->L - 1; l >= 0; --l) {
+    const int top = d->L - 1;
+    CMF_TRY(act_bwd(act_bwd_args(M, d->C[d->L], d->dout, d->lddout, L.z[top], L.bn[top], L.dU[top], L.partial), st));
+    for (int l = top; l >= 0; --l) {
         const int cin = d->C[l], cout = d->C[l + 1];
-        const float *b = L.bn[l];
+        const Bn &b = L.bn[l], in = l > 0 ? L.bn[l - 1] : Bn();
         CMF_CHECK_ARG(d->dw[l] && d->dgamma[l] && d->dbeta[l]);
-        if (d->acc_bn[l]) CMF_TRY(cmf_colsum_finalize(tiles128(M), cout, L.partial, L.sums, d->dbeta[l], d->dgamma[l], st));
-        else CMF_TRY(cmf_colsum_store(tiles128(M), 2 * cout, L.partial, L.sums, cout, d->dbeta[l], d->dgamma[l], st));
-        CMF_TRY(cmf_bn_bwd_apply(M, cout, L.dU[l], L.z[l], cout, b + 2 * cout, b, b + cout, d->training ? L.sums : nullptr, st));
-        // weight gradient: dZ^T act(x_in), deterministic split-K
-        const float *xin = l == 0 ? d->x : L.z[l - 1];
-        const long long ldin = l == 0 ? d->ldx : cin;
-        const float *bi = l > 0 ? L.bn[l - 1] : nullptr;
-        const int split = dw_split(M, cout, cin);
-        CMF_TRY(cmf_gemm(cout, cin, (int)M, 1, 0, L.dU[l], cout, xin, ldin, d->dw[l], cin, nullptr, nullptr, bi ? bi + 2 * cin : nullptr,
-                         bi ? bi + 3 * cin : nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, split,
-                         split > 1 ? L.splitk : nullptr, d->acc_w[l], st));
-        if (l > 0)                      // gradient w.r.t. the pre-activation of the layer below, masked, with its BN-backward sums
-            CMF_TRY(cmf_gemm((int)M, cin, cout, 0, 0, L.dU[l], cout, d->w[l], cin, L.dU[l - 1], cin, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                             L.partial, 1, L.z[l - 1], cin, bi + 2 * cin, bi + 3 * cin, bi, bi + cin, nullptr, 1, nullptr, 0, st));
-        else if (d->dx)
-            CMF_TRY(cmf_gemm((int)M, cin, cout, 0, 0, L.dU[0], cout, d->w[0], cin, d->dx, d->lddx, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                             nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0, st));
+        CMF_TRY(bn_grad_sums(bn_grad_args(d, l, tiles128(M), 2 * cout, cout, L.partial, L.sums), st));
+        CMF_TRY(cmf_bn_bwd_apply(M, cout, L.dU[l], L.z[l], cout, b.a, b.mean, b.invstd, d->training ? L.sums : nullptr, st));
+        // weight gradient dZ^T act(x_in); then the gradient w.r.t. the pre-activation of the layer below, masked, with its BN-backward
+        // sums -- or, for the first layer, the plain gradient of the input when it is wanted
+        CMF_TRY(dw_gemm(M, cout, cin, L.dU[l], l == 0 ? d->x : L.z[l - 1], l == 0 ? d->ldx : cin, in, d->dw[l], d->acc_w[l], L.splitk, st));
+        if (l > 0) CMF_TRY(dx_gemm(M, cout, cin, L.dU[l], d->w[l], L.dU[l - 1], cin, L.z[l - 1], in, L.partial, nullptr, st));
+        else if (d->dx) CMF_TRY(dx_gemm(M, cout, cin, L.dU[0], d->w[0], d->dx, d->lddx, nullptr, in, nullptr, nullptr, st));
     }
     return 0;
 }
@@ -1296,7 +1231,7 @@ extern "C" int cmf_setconv_bn_offsets(const cmf_setconv_desc *d, long long *offs
     // lay the arena out over a fake non-null base (Bump hands out NULL for a NULL base) and subtract it again
     float *const fake = reinterpret_cast<float *>(uintptr_t(1) << 40);
     const Layout L = make_layout(d, fake, nullptr, false);
-    for (int l = 0; l < 6; ++l) offsets6[l] = (long long)(L.bn[l] - fake);
+    for (int l = 0; l < 6; ++l) offsets6[l] = (long long)(L.bn[l].block() - fake);
     return 0;
 }
 

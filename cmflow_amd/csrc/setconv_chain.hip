@@ -452,7 +452,7 @@ int cmf_setconv_chain_infer_batch(int n, const CmfChainInferArgs *q, void *strea
 // internal (setconv_block.hip): the block's neighbour-slot layers as chain passes, when the shape is the chain's
 bool cmf_setconv_chain_supported(int N, int S, int O1, int C2, int C3, long long M)
 {
-    static const bool on = !(getenv("CMF_CHAIN") && getenv("CMF_CHAIN")[0] == '0');
+    static const bool on = cmf_env_on("CMF_CHAIN");
     return on && O1 == 32 && C2 == 32 && C3 == 64 && (S == 4 || S == 8 || S == 16 || S == 32) && M % 32 == 0 && ((long long)N * S) % 32 == 0;
 }
 // rows of `partial` / slabs a pass writes (the caller sizes scratch with the maxima)

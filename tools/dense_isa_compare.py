@@ -25,9 +25,10 @@ def kernels(path, mask_kernarg):
 
 
 def base(name):
-    """_Z<len><name>... -> <name> (template arguments and parameter types dropped)"""
+    """_Z<len><name>... -> <name> (template arguments and parameter types dropped); a nested name (_ZN...: a kernel in a namespace)
+    is its own base and is matched by its full name only"""
     m = re.match(r"_Z(\d+)", name)
-    return name[m.end():m.end() + int(m.group(1))]
+    return name[m.end():m.end() + int(m.group(1))] if m else name
 
 
 old_s, new_s = sys.argv[1], sys.argv[2]
