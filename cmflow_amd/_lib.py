@@ -27,6 +27,11 @@ SIGNATURES = {
     "cmf_global_max_cat_counted": [_ci, _ci, _ci, _vp, _ll, _vp, _ll, _vp, _vp, _vp],
     "cmf_ego_refine_counted": [_ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_eval_metrics_counted": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
+    "cmf_radar_loss_counted_workspace": [_ci, _ci, _ci, _ci],
+    "cmf_radar_loss_counted_workspace_tiled": [_ci, _ci, _ci, _ci],
+    "cmf_radar_loss_counted": [_vp, _vp],
+    "cmf_radar_loss_counted_tiled": [_vp, _vp],
+    "cmf_pseudo_labels_counted": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp],
     "cmf_group_points": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp],
     "cmf_group_points_grad": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp],
     "cmf_query_and_group": [_ci, _ci, _ci, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -130,7 +135,8 @@ SIGNATURES = {
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }
-RESTYPES = {"cmf_mem_stats": _ll, "cmf_radar_loss_workspace_nb": _ll, "cmf_radar_loss_workspace_tiled": _ll, "cmf_gemm_trace_read": _ll, "cmf_gemm_profile_records": _ll}
+RESTYPES = {"cmf_mem_stats": _ll, "cmf_radar_loss_counted_workspace": _ll, "cmf_radar_loss_counted_workspace_tiled": _ll,
+            "cmf_radar_loss_workspace_nb": _ll, "cmf_radar_loss_workspace_tiled": _ll, "cmf_gemm_trace_read": _ll, "cmf_gemm_profile_records": _ll}
 
 
 class GemmLaunchRecord(ctypes.Structure):
@@ -175,6 +181,17 @@ class RadarLossDesc(ctypes.Structure):
                 ("w_self", _cf), ("w_em", _cf), ("w_ms", _cf), ("w_opt", _cf), ("w_dyn", _cf),
                 ("zeta", _cf), ("alpha", _cf), ("num_nb", _ci), ("lower_bound", _cf), ("self_only", _ci),
                 ("items", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp)]
+
+
+class RadarLossCountedDesc(ctypes.Structure):
+    """cmf_radar_loss_counted_desc of include/cmflow_hip.h"""
+    _fields_ = [("B", _ci), ("N1max", _ci), ("N2max", _ci), ("n1", _vp), ("n2", _vp),
+                ("pc1", _vp), ("pred_f", _vp), ("gt_f", _vp), ("pc2", _vp),
+                ("vel1", _vp), ("mseg_pre", _vp), ("mseg_gt", _vp), ("dyn_mask", _vp), ("radar_u", _vp), ("radar_v", _vp),
+                ("opt", _vp), ("pre_trans", _vp), ("gt_trans", _vp), ("camera_inverse", _vp), ("t_camera_radar", _vp),
+                ("w_self", _cf), ("w_em", _cf), ("w_ms", _cf), ("w_opt", _cf), ("w_dyn", _cf),
+                ("zeta", _cf), ("alpha", _cf), ("num_nb", _ci), ("lower_bound", _cf), ("self_only", _ci),
+                ("items", _vp), ("items_mean", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp)]
 
 
 def build(force: bool = False) -> str:

@@ -179,20 +179,27 @@ __global__ __launch_bounds__(64) void eval_finalize_counted_kernel(int b, int ld
 // Pseudo labels of the training step (main_util.py:63-67): dyn_mask = extract_dynamic_from_fg (:209-225) and the
 // motion-segmentation label mseg_label_RRV (:253-265), merged as where(dyn_mask == 1, mseg, dyn_mask).
 // One workgroup per sample (the RRV threshold is relative to the sample's mean residual).
+// COUNTED (cmf_pseudo_labels_counted, ragged samples): the sample's rows are ld apart and the mean residual -- the only reduction over
+// a sample in main_util.py:209-225,253-265 -- runs over its first cnt[bs] points; padded slots of the outputs are written as 0.
+// Dense: cnt is not read and n == ld.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool COUNTED>
 __global__ __launch_bounds__(EV_THREADS) void pseudo_label_kernel(
-    int n, const float *__restrict__ pc1, const float *__restrict__ gt_trans, const float *__restrict__ vel1,
+    int ld, const float *__restrict__ pc1, const float *__restrict__ gt_trans, const float *__restrict__ vel1,
     const float *__restrict__ interval, const float *__restrict__ fg_mask, const float *__restrict__ flow_label,
-    float vr_thres, float *__restrict__ dyn_mask, float *__restrict__ mseg_gt, float *__restrict__ residual_out)
+    float vr_thres, float *__restrict__ dyn_mask, float *__restrict__ mseg_gt, float *__restrict__ residual_out,
+    const int *__restrict__ cnt)
 {
     extern __shared__ float resid[];                 // [n]
     __shared__ float redf[EV_THREADS / 64];
     const int bs = blockIdx.x, tid = threadIdx.x;
+    const int n = ld;                                // row stride
+    const int nv = COUNTED ? max(0, min(cnt[bs], ld)) : ld;
     const float *T = gt_trans + (size_t)bs * 16;
     const float *p = pc1 + (size_t)bs * 3 * n;
     const float dt = interval[bs];
     float sum = 0.f;
-    for (int i = tid; i < n; i += EV_THREADS) {
+    for (int i = tid; i < nv; i += EV_THREADS) {
         const float x = p[i], y = p[n + i], z = p[2 * n + i];
         // rigid_to_flow (models/cmflow.py:51-55): (T [p;1])[:3] - p
         const float fx = (((T[0] * x + T[1] * y) + T[2] * z) + T[3]) - x;
@@ -217,13 +224,19 @@ __global__ __launch_bounds__(EV_THREADS) void pseudo_label_kernel(
     float tot = 0.f;
 #pragma unroll
     for (int w = 0; w < EV_THREADS / 64; ++w) tot += redf[w];
-    const float mean = tot / (float)n;
-    for (int i = tid; i < n; i += EV_THREADS) {
+    const float mean = tot / (float)nv;
+    for (int i = tid; i < nv; i += EV_THREADS) {
         const float rrv = ((resid[i] - mean) < vr_thres) ? 1.f : 0.f;
         const float d = dyn_mask[(size_t)bs * n + i];
         mseg_gt[(size_t)bs * n + i] = (d == 1.f) ? rrv : d;
         if (residual_out) residual_out[(size_t)bs * n + i] = resid[i];
     }
+    if (COUNTED)
+        for (int i = nv + tid; i < ld; i += EV_THREADS) {
+            dyn_mask[(size_t)bs * n + i] = 0.f;
+            mseg_gt[(size_t)bs * n + i] = 0.f;
+            if (residual_out) residual_out[(size_t)bs * n + i] = 0.f;
+        }
 }
 
 extern "C" int cmf_pseudo_labels(int b, int n, const float *pc1, const float *gt_trans, const float *vel1,
@@ -236,11 +249,29 @@ extern "C" int cmf_pseudo_labels(int b, int n, const float *pc1, const float *gt
     static CmfPerDevice attr_set;                       // the dynamic-LDS limit is per (function, device)
     int attr_dev;
     if (attr_set.need(attr_dev)) {
-        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
+        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
         attr_set.done(attr_dev);
     }
-    hipLaunchKernelGGL(pseudo_label_kernel, dim3(b), dim3(EV_THREADS), (size_t)n * sizeof(float), (hipStream_t)stream,
-                       n, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual);
+    hipLaunchKernelGGL(pseudo_label_kernel<false>, dim3(b), dim3(EV_THREADS), (size_t)n * sizeof(float), (hipStream_t)stream,
+                       n, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, (const int *)nullptr);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_pseudo_labels_counted(int b, int nmax, const int *n1, const float *pc1, const float *gt_trans, const float *vel1,
+                                         const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
+                                         float *dyn_mask, float *mseg_gt, float *residual, void *stream)
+{
+    CMF_CHECK_ARG(b >= 0 && nmax > 0 && nmax <= 36000);
+    if (b == 0) return 0;
+    CMF_CHECK_ARG(n1 && pc1 && gt_trans && vel1 && interval && fg_mask && flow_label && dyn_mask && mseg_gt);
+    static CmfPerDevice attr_set;
+    int attr_dev;
+    if (attr_set.need(attr_dev)) {
+        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
+        attr_set.done(attr_dev);
+    }
+    hipLaunchKernelGGL(pseudo_label_kernel<true>, dim3(b), dim3(EV_THREADS), (size_t)nmax * sizeof(float), (hipStream_t)stream,
+                       nmax, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, n1);
     return cmf_launch_status();
 }
 

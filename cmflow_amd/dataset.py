@@ -219,6 +219,14 @@ def as_batch_dict(info):
     return dict(zip(keys, info))
 
 
+def as_batch_dict_ragged(info):
+    """The tuple of extract_data_info_ragged as the dict losses.make_labels_ragged / RadarFlowLoss.forward_ragged take: the keys of
+    as_batch_dict plus the count tensors ``n1``, ``n2``."""
+    d = as_batch_dict(info[:11])
+    d["n1"], d["n2"] = info[11], info[12]
+    return d
+
+
 def write_sample(path, pc1, pc2, gt_labels, pse_labels, gt_mask, pse_mask, trans, opt_flow=None, radar_u=None, radar_v=None):
     """Write one sample file in the format above (pc1, pc2: (n,5) arrays x,y,z,RCS,v_r)."""
     ls = lambda a: np.asarray(a).tolist()

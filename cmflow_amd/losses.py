@@ -39,6 +39,29 @@ def make_labels(batch, vr_thres):
     return dyn_mask.to(batch["fg_mask"].dtype), mseg_gt
 
 
+def make_labels_ragged(batch, vr_thres):
+    """make_labels for a RAGGED batch (``dataset.as_batch_dict_ragged``: pc1 / ft1 (B,3,Nmax1), fg_mask (B,Nmax1), flow_label
+    (B,Nmax1,3) padded, ``n1`` (B,) int32 on the device): one launch of cmf_pseudo_labels_counted.  Sample i's slices [:n1[i]] are
+    bit-identical to make_labels on the truncated sample at B = 1 (the one reduction over a sample, the mean residual of
+    main_util.py:260, runs over its valid points); padded slots of both outputs are 0."""
+    pc1, n1 = batch["pc1"], batch["n1"]
+    B, _, N = pc1.shape
+    if n1.dtype != torch.int32 or n1.shape != (B,) or n1.device != pc1.device:
+        raise ValueError("make_labels_ragged: n1 is a (B,) int32 tensor on the inputs' device")
+    if not pc1.is_cuda:
+        raise RuntimeError("cmflow_amd.losses.make_labels_ragged runs on the GPU only (got %s tensors)" % pc1.device)
+    f32 = torch.float32
+    c = lambda t: t.to(f32).contiguous()
+    pc, T, vel, dt = c(pc1), c(batch["gt_trans"]), c(batch["ft1"][:, 0]), c(batch["interval"])
+    fg, fl = c(batch["fg_mask"]), c(batch["flow_label"])
+    dyn_mask, mseg_gt = torch.empty(B, N, dtype=f32, device=pc1.device), torch.empty(B, N, dtype=f32, device=pc1.device)
+    p = lambda t: _lib.dev_ptr(t, f32)
+    _lib.check(_lib.lib().cmf_pseudo_labels_counted(B, N, _lib.dev_ptr(n1.contiguous(), torch.int32), p(pc), p(T), p(vel), p(dt),
+                                                    p(fg), p(fl), vr_thres, p(dyn_mask), p(mseg_gt), None, _lib.stream_ptr()),
+               "cmf_pseudo_labels_counted")
+    return dyn_mask.to(batch["fg_mask"].dtype), mseg_gt
+
+
 
 MAX_N = 65536                                # include/cmflow_hip.h CMF_RADAR_LOSS_MAX_N
 NUM_NB = (4, 8, 16)                          # csrc/loss.hip: the neighbour counts the kernels are instantiated for
@@ -105,6 +128,60 @@ class RadarFlowLossFn(Function):
         return out[0], out[1], out[2], None, None
 
 
+class RadarFlowLossRaggedFn(Function):
+    """mean total, mean items, per-sample items = cmf_radar_loss_counted(...) on a padded batch with per-sample counts; the kernel
+    writes d (mean total) / d (pred_f, pre_trans, mseg_pre) in the same pass (padded slots 0), backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, pred_f, pre_trans, mseg_pre, data, hyper):
+        pc1, pc2, n1, n2 = data["pc1"], data["pc2"], data["n1"], data["n2"]
+        B, _, N1 = pc1.shape
+        N2 = pc2.shape[2]
+        dev = pc1.device
+        f32 = torch.float32
+        t = {k: v.contiguous() for k, v in data.items()}
+        pred_f = pred_f.contiguous()
+        pre_trans = pre_trans.contiguous() if pre_trans is not None else None
+        mseg_pre = mseg_pre.contiguous() if mseg_pre is not None else None
+        for k, v in list(t.items()) + [("pred_f", pred_f), ("pre_trans", pre_trans), ("mseg_pre", mseg_pre)]:
+            _lib.dev_ptr(v, torch.int32 if k in ("n1", "n2") else f32)   # device / dtype / density checks (no CPU fallback)
+        need = any(ctx.needs_input_grad[:3])
+        d = _lib.RadarLossCountedDesc()
+        d.B, d.N1max, d.N2max = B, N1, N2
+        d.n1, d.n2 = t["n1"].data_ptr(), t["n2"].data_ptr()
+        d.self_only = int(hyper.get("self_only", False))
+        d.pc1, d.pc2, d.pred_f, d.vel1 = t["pc1"].data_ptr(), t["pc2"].data_ptr(), pred_f.data_ptr(), t["vel1"].data_ptr()
+        if not d.self_only:
+            d.gt_f, d.mseg_pre, d.mseg_gt = t["gt_f"].data_ptr(), mseg_pre.data_ptr(), t["mseg_gt"].data_ptr()
+            d.dyn_mask, d.radar_u, d.radar_v = t["dyn_mask"].data_ptr(), t["radar_u"].data_ptr(), t["radar_v"].data_ptr()
+            d.opt, d.pre_trans, d.gt_trans = t["opt"].data_ptr(), pre_trans.data_ptr(), t["gt_trans"].data_ptr()
+            d.camera_inverse, d.t_camera_radar = t["camera_inverse"].data_ptr(), t["t_camera_radar"].data_ptr()
+        d.w_self, d.w_em, d.w_ms, d.w_opt, d.w_dyn = hyper["w"]
+        d.zeta, d.alpha, d.num_nb, d.lower_bound = hyper["zeta"], hyper["alpha"], hyper["num_nb"], hyper["lower_bound"]
+        per_sample = torch.empty(B, 9, dtype=f32, device=dev)
+        items = torch.empty(9, dtype=f32, device=dev)
+        tiled = bool(hyper.get("tiled", False))
+        size = _lib.lib().cmf_radar_loss_counted_workspace_tiled if tiled else _lib.lib().cmf_radar_loss_counted_workspace
+        ws = torch.empty(size(B, N1, N2, int(hyper["num_nb"])), dtype=f32, device=dev)
+        d.items, d.items_mean, d.workspace = per_sample.data_ptr(), items.data_ptr(), ws.data_ptr()
+        if need:
+            g_f = torch.empty(B, 3, N1, dtype=f32, device=dev)
+            g_t = torch.empty(B, 4, 4, dtype=f32, device=dev) if pre_trans is not None else None
+            g_m = torch.empty(mseg_pre.shape, dtype=f32, device=dev) if mseg_pre is not None else None
+            d.d_pred_f = g_f.data_ptr()
+            d.d_pre_trans = g_t.data_ptr() if g_t is not None else None
+            d.d_mseg_pre = g_m.data_ptr() if g_m is not None else None
+            ctx.grads = (g_f, g_t, g_m)
+        call = _lib.lib().cmf_radar_loss_counted_tiled if tiled else _lib.lib().cmf_radar_loss_counted
+        _lib.check(call(ctypes.addressof(d), _lib.stream_ptr()), "cmf_radar_loss_counted")
+        ctx.mark_non_differentiable(items, per_sample)
+        return items[0], items, per_sample
+
+    @staticmethod
+    def backward(ctx, g_total, _g_items, _g_per_sample):
+        return RadarFlowLossFn.backward(ctx, g_total, None)
+
+
 SELF_ITEM_KEYS = ITEM_KEYS[:4]
 
 
@@ -149,3 +226,54 @@ class RadarFlowLoss(Module):
                      num_nb=self.num_nb, lower_bound=self.lower_bound, tiled=self.tiled)
         total, items = RadarFlowLossFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
         return total, {k: items[i + 1] for i, k in enumerate(ITEM_KEYS)}
+
+    # ---- ragged batches: whole frames of their own sizes (CMFlow.forward_ragged, dataset.collate_ragged) ----------------------------
+    def _check_ragged(self, pc1, pc2, pred_f, npoints1, npoints2, validate):
+        if pc1.dim() != 3 or pc2.dim() != 3 or pc1.shape[1] != 3 or pc2.shape[1] != 3 or pc2.shape[0] != pc1.shape[0] or \
+                pred_f.shape != pc1.shape:
+            raise ValueError("forward_ragged: pc1 / pred_f are (B,3,Nmax1), pc2 (B,3,Nmax2)")
+        B, _, N1 = pc1.shape
+        N2 = pc2.shape[2]
+        for n in (npoints1, npoints2):
+            if not torch.is_tensor(n) or n.dtype != torch.int32 or n.shape != (B,) or n.device != pc1.device:
+                raise ValueError("forward_ragged: npoints1 / npoints2 are (B,) int32 tensors on the inputs' device")
+        if self.num_nb not in NUM_NB or not (self.num_nb < N1 <= MAX_N) or not (1 <= N2 <= MAX_N):
+            raise ValueError("cmf_radar_loss_counted: num_nb in %s, num_nb < Nmax1 <= %d and 1 <= Nmax2 <= %d (got Nmax1 = %d, "
+                             "Nmax2 = %d, num_nb = %d)" % (NUM_NB, MAX_N, MAX_N, N1, N2, self.num_nb))
+        if validate:                                                # a device -> host sync
+            lo1, hi1, lo2, hi2 = (int(v) for v in torch.stack((npoints1.min(), npoints1.max(), npoints2.min(), npoints2.max())).tolist())
+            if lo1 <= self.num_nb or hi1 > N1:
+                raise ValueError("forward_ragged: npoints1 must lie in [%d, %d] (the smoothness term takes %d neighbours besides the "
+                                 "point itself; the reference's top-k raises below that); got [%d, %d]"
+                                 % (self.num_nb + 1, N1, self.num_nb, lo1, hi1))
+            if lo2 < 1 or hi2 > N2:
+                raise ValueError("forward_ragged: npoints2 must lie in [1, %d]; got [%d, %d]" % (N2, lo2, hi2))
+        if not pc1.is_cuda:
+            raise RuntimeError("cmflow_amd.losses.RadarFlowLoss runs on the GPU only (got %s tensors)" % pc1.device)
+
+    def forward_ragged(self, pc1, pc2, pred_f, vel1, npoints1, npoints2, gt_f=None, pre_trans=None, mseg_pre=None, gt_trans=None,
+                       mseg_gt=None, dyn_mask=None, radar_u=None, radar_v=None, opt=None, validate=False):
+        """The loss of B whole frames of their own sizes in one call (cmf_radar_loss_counted).  pc1, pred_f, gt_f (B,3,Nmax1), pc2
+        (B,3,Nmax2), per-point tensors of cloud 1 (B,Nmax1[,2]) padded; npoints1, npoints2 (B,) int32 on the device,
+        num_nb < npoints1[i] <= Nmax1, 1 <= npoints2[i] <= Nmax2.
+        -> (total, items, per_sample): per_sample (B,9) holds for sample i what ``forward`` returns at B = 1 on the truncated sample
+        (column 0 the total, columns 1.. in the order of ITEM_KEYS); items / total are their means over the B samples (the
+        reference's test protocol at batch size 1) -- NOT the dense batch loss, which pools the three masked terms over the batch.
+        total is differentiable w.r.t. pred_f, pre_trans, mseg_pre; padded slots of the gradients are 0.  Padded input slots must
+        be finite and influence nothing.  validate=True checks the counts on the host (ValueError; a device -> host sync), otherwise
+        they are trusted: the kernels clamp them to [num_nb + 1, Nmax1] / [1, Nmax2], so a wrong count gives wrong numbers, not a
+        wild access.  Without gt_f: the three self-supervised terms (model 'raflow'), as in ``forward``."""
+        self._check_ragged(pc1, pc2, pred_f, npoints1, npoints2, validate)
+        if gt_f is None:
+            hyper = dict(w=(self.w_self, 0.0, 0.0, 0.0, 0.0), zeta=self.zeta, alpha=self.alpha, num_nb=self.num_nb,
+                         lower_bound=0.0, self_only=True, tiled=self.tiled)
+            total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, None, None, dict(pc1=pc1, pc2=pc2, vel1=vel1, n1=npoints1,
+                                                                                            n2=npoints2), hyper)
+            return total, {k: items[i + 1] for i, k in enumerate(SELF_ITEM_KEYS)}, per_sample
+        data = dict(pc1=pc1, pc2=pc2, gt_f=gt_f, vel1=vel1, gt_trans=gt_trans, mseg_gt=mseg_gt.to(pc1.dtype),
+                    dyn_mask=dyn_mask.to(pc1.dtype), radar_u=radar_u, radar_v=radar_v, opt=opt,
+                    camera_inverse=self.camera_inverse, t_camera_radar=self.t_camera_radar, n1=npoints1, n2=npoints2)
+        hyper = dict(w=(self.w_self, self.w_em, self.w_ms, self.w_opt, self.w_dyn), zeta=self.zeta, alpha=self.alpha,
+                     num_nb=self.num_nb, lower_bound=self.lower_bound, tiled=self.tiled)
+        total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
+        return total, {k: items[i + 1] for i, k in enumerate(ITEM_KEYS)}, per_sample

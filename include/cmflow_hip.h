@@ -674,6 +674,56 @@ int cmf_eval_metrics_counted(int b, int n, const int *cnt, const float *pc, cons
                              const float *pred_m, const float *gt_trans, const float *pred_trans,
                              float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream);
 
+/* ---- ragged batches: the loss and the pseudo labels on whole frames ---------------------------------------------------------
+ * cmf_radar_loss_counted: cmf_radar_loss on B padded samples of their own sizes.  Everything indexed by the points of cloud 1 (pc1,
+ *   pred_f, gt_f, the per-point scalars, opt, d_pred_f, d_mseg_pre) has row stride N1max, pc2 has row stride N2max; n1, n2 (B ints in
+ *   DEVICE memory) are the valid counts.  items (B,9): for sample i the nine items cmf_radar_loss returns with B = 1 on the truncated
+ *   sample (pc1[i,:,:n1[i]], pc2[i,:,:n2[i]], ...): every mean over points divides by n1[i] (the cloud-2 side of the Chamfer term by
+ *   n2[i], its density masks average over the other cloud's valid points), the smoothness factor N is n1[i], the class counts and
+ *   masked means of the motion-seg / optical / dynamic terms run over the sample's valid points.  items_mean[9]: their mean over the
+ *   B samples, folded in index order -- the reference's protocol at batch size 1, as cmf_eval_metrics_counted defines its metrics.
+ *   This is NOT cmf_radar_loss on a batch of equal-sized samples: the dense loss (like the reference) pools the class counts and
+ *   the masked sums of those three terms over the whole batch before dividing; here every sample divides by its own.
+ *   The gradients are those of items_mean[0]: the B = 1 gradients of the truncated sample, multiplied by 1/B as the last operation
+ *   (exactly the dense B = 1 values / B when B is a power of two); padded slots of d_pred_f and d_mseg_pre are written as 0.
+ *   With n1[i] == n2[i] the items of sample i are bit-identical to the dense call of the same form (LDS / tiled) at B = 1; with
+ *   n1 != n2 the cloud-2 Chamfer summands are weighted by (float)n1 / (float)n2 (exactly 1 in the equal case) before the one
+ *   division by n1 -- one more rounding per summand.  Slots behind a count are read as points at infinite distance with zero
+ *   weight; their content does not influence any output as long as it is finite.  Counts are clamped inside the kernels to
+ *   [num_nb + 1, N1max] and [1, N2max]: a wrong count gives wrong numbers, never an access outside the tensors.
+ *   Forms as cmf_radar_loss: max(N1max, N2max) <= 704 with num_nb == 8 keeps a sample in one workgroup's LDS, everything else up to
+ *   CMF_RADAR_LOSS_MAX_N takes the tiled kernels; cmf_radar_loss_counted_tiled forces the tiled form.  No floating-point atomics:
+ *   results are bit-reproducible and independent of the padded sizes and of the other samples in the batch.
+ * cmf_pseudo_labels_counted: cmf_pseudo_labels with rows nmax apart and the one reduction over a sample it contains -- the mean
+ *   residual of mseg_label_RRV (main_util.py:260); extract_dynamic_from_fg (:209-225) is per point -- over the first n1[s] points.
+ *   Valid slots are bit-identical to cmf_pseudo_labels(b = 1, n = n1[s]) on the truncated sample; padded slots of dyn_mask, mseg_gt
+ *   (and residual) are written as 0 -- cmf_radar_loss_counted never reads them.  n1 is clamped to [0, nmax]. */
+typedef struct cmf_radar_loss_counted_desc {
+    int B, N1max, N2max;
+    const int *n1, *n2;                                                        /* (B) device */
+    const float *pc1, *pred_f, *gt_f;                                          /* (B,3,N1max) */
+    const float *pc2;                                                          /* (B,3,N2max) */
+    const float *vel1, *mseg_pre, *mseg_gt, *dyn_mask, *radar_u, *radar_v;     /* (B,N1max) */
+    const float *opt;                                                          /* (B,N1max,2) */
+    const float *pre_trans, *gt_trans;                                         /* (B,4,4) */
+    const float *camera_inverse;                                               /* (3,3) inverse intrinsics */
+    const float *t_camera_radar;                                               /* (4,4) */
+    float w_self, w_em, w_ms, w_opt, w_dyn;
+    float zeta, alpha; int num_nb; float lower_bound;
+    int self_only;                                                             /* as in cmf_radar_loss_desc */
+    float *items;                                                              /* (B,9) per sample */
+    float *items_mean;                                                         /* [9] */
+    float *d_pred_f, *d_pre_trans, *d_mseg_pre;                                /* (B,3,N1max), (B,4,4), (B,N1max) or NULL */
+    float *workspace;                                                          /* cmf_radar_loss_counted_workspace floats */
+} cmf_radar_loss_counted_desc;
+long long cmf_radar_loss_counted_workspace(int b, int n1max, int n2max, int num_nb);
+int cmf_radar_loss_counted(const cmf_radar_loss_counted_desc *d, void *stream);
+int cmf_radar_loss_counted_tiled(const cmf_radar_loss_counted_desc *d, void *stream);   /* workspace: ..._workspace_tiled */
+long long cmf_radar_loss_counted_workspace_tiled(int b, int n1max, int n2max, int num_nb);
+int cmf_pseudo_labels_counted(int b, int nmax, const int *n1, const float *pc1, const float *gt_trans, const float *vel1,
+                              const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
+                              float *dyn_mask, float *mseg_gt, float *residual, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
