@@ -64,6 +64,7 @@ __device__ void svd3(const double *H, double *U, double *S, double *V)
     for (int j = 0; j < 3; ++j) {
         good[j] = S[j] > 1e-14 * smax && S[j] > 0.0;
         if (good[j]) for (int i = 0; i < 3; ++i) U[i * 3 + j] = A[i * 3 + j] / S[j];
+        else S[j] = 0.0;        // rounding residue of a null direction: the backward's s_i + s_j must not divide by it
     }
     // rank-deficient H: complete U to an orthonormal basis (the rotation is not unique there;
     // any completion is a valid SVD)

@@ -81,7 +81,13 @@ int cmf_knn(int b, int n, int s, int nsample, const float *xyz, const float *new
 
 /* WeightedKabsch (models/cmflow.py:128-169).  A, Bm (b,3,n) point sets, W (b,n) weights
  * (normalised by the caller, cmflow.py:105-106) -> trans (b,4,4).  aux (b,32) doubles receives
- * {U,S,V of H, cA, cB, D} for the backward pass (may be NULL). */
+ * {U,S,V of H, cA, cB, D} for the backward pass (may be NULL).
+ * Rank-deficient H (fewer than three independent weighted points, a collinear or exactly planar cloud, all weights
+ * zero): the rotation is not unique there.  The solve returns a PROPER rotation (R^T R = I, det R = +1, finite) that
+ * agrees with the determined subspace and completes the rest orthonormally (H = 0: R = I), t = cB - R cA as always,
+ * bottom row (0,0,0,1).  Singular values below 1e-14 of the largest are stored as exact zeros in aux, so the backward
+ * pass (which divides by s_i + s_j) sends no gradient through a pair of undetermined directions: every gradient stays
+ * finite.  tests/test_gpu_kabsch.py pins these properties, not the particular completion. */
 int cmf_weighted_kabsch(int b, int n, const float *A, const float *Bm, const float *W,
                         float *trans, double *aux, void *stream);
 
