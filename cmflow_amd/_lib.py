@@ -27,6 +27,8 @@ SIGNATURES = {
     "cmf_global_max_cat_counted": [_ci, _ci, _ci, _vp, _ll, _vp, _ll, _vp, _vp, _vp],
     "cmf_ego_refine_counted": [_ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_eval_metrics_counted": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
+    "cmf_ego_refine_grad_counted": [_ci, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_global_max_cat_grad_counted": [_ci, _ci, _ci, _vp, _ll, _vp, _vp, _ll, _vp, _vp],
     "cmf_radar_loss_counted_workspace": [_ci, _ci, _ci, _ci],
     "cmf_radar_loss_counted_workspace_tiled": [_ci, _ci, _ci, _ci],
     "cmf_radar_loss_counted": [_vp, _vp],

@@ -185,11 +185,16 @@ class CMFlow(nn.Module):
     RAGGED_MAX_POINTS = 1024                       # the counted one-scan ball query (cmflow_hip.h)
 
     def _check_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate):
+        """forward_ragged's own mode checks (inference only), then the shared shape and count checks."""
         if self.training:
             raise RuntimeError("forward_ragged is inference only: call net.eval() first (train-mode BatchNorm statistics over padded "
                                "rows are a different computation)")
         if torch.is_grad_enabled():
             raise RuntimeError("forward_ragged is inference only: call it under torch.no_grad()")
+        self._check_ragged_shapes(pc1, pc2, feature1, feature2, npoints1, npoints2, validate)
+
+    def _check_ragged_shapes(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate):
+        """The shape and count rules of a ragged batch, shared by forward_ragged and forward_ragged_train."""
         B, _, N1 = pc1.shape
         N2 = pc2.shape[2]
         if pc2.shape[0] != B or feature1.shape[0] != B or feature2.shape[0] != B or feature1.shape[2] != N1 or feature2.shape[2] != N2:
@@ -218,11 +223,12 @@ class CMFlow(nn.Module):
         a1 = a1p[:, :, :feature1.shape[1]]
         # both clouds padded to one size share ONE call of the (weight-shared) first encoder, as in the dense eval path
         f12 = self.mse_layer.forward_pm_ragged(torch.cat((x1, x2), dim=0), torch.cat((a1p, a2p), dim=0), torch.cat((n1, n2)))
+        # (with autograd recording -- forward_ragged_train -- every node below is the dense path's or its counted sibling)
         f1, f2 = FB.global_max_cat_counted(f12[:B], n1), FB.global_max_cat_counted(f12[B:], n2)     # (B,Nm,512)
         cor = self.fc_layer.forward_pm(x1, x2, f1, f2, n1, n2)                                 # (B,Nm,512)
         n_grad, n_tail = f1.shape[2] + cor.shape[2], a1.shape[2]
         emb = torch.cat((f1, cor, a1, a1.new_zeros(B, Nm, -(n_grad + n_tail) % 16)), dim=2)
-        prop = self._second_encoder().forward_pm_ragged(x1, emb, n1, n_tail=n_tail)            # (B,Nm,256)
+        prop = self._second_encoder().forward_pm_ragged(x1, emb, n1, n_tail=n_tail, n_grad=n_grad)     # (B,Nm,256)
         self.last = {"pc1_features": f1[:, :N1, :256].transpose(1, 2), "pc2_features": f2[:, :N2, :256].transpose(1, 2),
                      "cor_features": cor[:, :N1].transpose(1, 2), "prop_features": prop[:, :N1].transpose(1, 2)}
         return prop
@@ -231,15 +237,27 @@ class CMFlow(nn.Module):
         """cmflow.py:89-91: cat(prop, max over the sample's valid points) as (B,512,Nm)."""
         return FB.global_max_cat_counted(prop, n1).transpose(1, 2), None
 
-    def _forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat_prev):
-        self._check_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate)
+    def _forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat_prev, label_m=None, train=False):
+        if train:
+            self._check_ragged_train(pc1, pc2, feature1, feature2, npoints1, npoints2, label_m, validate)
+        else:
+            self._check_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate)
         N1 = pc1.shape[2]
         prop = self._propagate_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2)
         Nm = prop.shape[1]
         final_features, gfeat = self._final_features_ragged(prop, npoints1, gfeat_prev)
         output, stat_cls = self._head_outputs(final_features)
         pc1m = pc1 if N1 == Nm else torch.nn.functional.pad(pc1, (0, Nm - N1))
-        pre_trans, sf_agg, mask, stat = ego_refine_counted(output, pc1m, stat_cls.squeeze(1), npoints1, self.score_eps or 0.0, self.stat_thres)
+        scores = stat_cls.squeeze(1)
+        if label_m is not None:                                     # forward(..., label_m, 'train'): the label is the ego-motion score
+            scores = label_m.detach().to(scores.dtype)
+            scores = scores if N1 == Nm else torch.nn.functional.pad(scores, (0, Nm - N1))
+        pre_trans, sf_agg, mask, stat = ego_refine_counted(output, pc1m, scores, npoints1, self.score_eps or 0.0, self.stat_thres)
+        if train:
+            # the head's own scores with the padded slots zeroed (what `stat` is when the head's scores went into the solve), as a
+            # differentiable select: a padded slot's gradient stops here
+            valid = torch.arange(Nm, device=pc1.device).unsqueeze(0) < npoints1.unsqueeze(1)
+            stat = stat_cls.squeeze(1).masked_fill(~valid, 0.0)
         if N1 != Nm:
             sf_agg, stat, mask = sf_agg[:, :, :N1].contiguous(), stat[:, :N1].contiguous(), mask[:, :N1].contiguous()
         return sf_agg, stat.unsqueeze(1), pre_trans, mask, gfeat
@@ -255,6 +273,33 @@ class CMFlow(nn.Module):
         on the host (ValueError) -- a device -> host synchronisation; without it the counts are trusted (the kernels clamp them to the
         padded size, so a wrong count gives wrong numbers, not a wild access)."""
         return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, None)[:4]
+
+
+    # ---- ragged batches in training: the reference's regime after its first epoch -- BatchNorm on its running statistics while
+    # gradients flow (train_one_epoch never calls net.train(), main_util.py:39-76,96).  Every layer is then row-wise in both
+    # directions: a padded row carries an exactly zero gradient and a valid row never reads a padded one.  The existing backward
+    # kernels are correct on the padded rows as they are (zero rows add +-0 to every weight-gradient contraction and scatter); the two
+    # places where gradients fan in over a sample -- the ego-motion solve and the global max -- have counted backward kernels.
+    def _check_ragged_train(self, pc1, pc2, feature1, feature2, npoints1, npoints2, label_m, validate):
+        if self.training:
+            raise RuntimeError("forward_ragged_train needs eval-mode BatchNorm: call net.eval() first (gradients flow through the "
+                               "running statistics, as in every epoch of the reference after the first; batch statistics over padded "
+                               "rows are a different computation)")
+        self._check_ragged_shapes(pc1, pc2, feature1, feature2, npoints1, npoints2, validate)
+        if label_m is not None and (label_m.shape != (pc1.shape[0], pc1.shape[2]) or label_m.device != pc1.device):
+            raise ValueError("forward_ragged_train: label_m is (B,Nmax1) on the inputs' device, or None")
+
+    def forward_ragged_train(self, pc1, pc2, feature1, feature2, npoints1, npoints2, label_m, validate=False):
+        """forward_ragged for training whole frames: works with autograd recording, under eval-mode BatchNorm (net.eval(); RuntimeError
+        in train mode).  Shapes and counts as forward_ragged; label_m (B,Nmax1) or None is the ego-motion score exactly as in
+        forward(..., label_m, 'train').  -> (sf_agg (B,3,Nmax1), mseg_pre (B,1,Nmax1), pre_trans (B,4,4), mask (B,Nmax1) bool): for
+        sample i the slices [..., :npoints1[i]] are what forward(pc1[i:i+1, :, :n1], ..., label_m[i:i+1, :n1], 'train') returns in
+        eval mode; padded output slots are zeros and receive zero gradient.  Padded slots of the inputs and of label_m influence neither
+        a valid output nor any parameter gradient as long as nothing overflows on them: zeros are recommended, anything up to the
+        magnitude of the data (the tests go to +-1e4) is safe; a huge finite value that reaches Inf inside the network would turn
+        the zero gradient of its row into NaN (0 * Inf) in every weight-gradient contraction, and is not caught.  Under
+        torch.no_grad() with label_m=None the result is forward_ragged's."""
+        return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, None, label_m, True)[:4]
 
 
 class CMFlow_T(CMFlow):
@@ -289,13 +334,26 @@ class CMFlow_T(CMFlow):
         gfeat = FB.global_max_cat_counted(prop, n1)[:, 0, C:]
         if gfeat_prev is None:
             gfeat_prev = torch.zeros_like(gfeat)
-        gfeat_new = self.gru(gfeat.unsqueeze(0), gfeat_prev.unsqueeze(0))[0].squeeze(0)
+        # forward_ragged_train records under eval(): the GRU has no dropout and no statistics, its mode changes nothing but MIOpen's
+        # RNN, which keeps the reserve space its backward needs only in training mode -- the flag of this one module, this one call
+        # (module state: like nn.Module.train() it is not for two threads in one network at a time)
+        mode = self.gru.training
+        self.gru.training = mode or (torch.is_grad_enabled() and (gfeat.requires_grad or gfeat_prev.requires_grad))
+        try:
+            gfeat_new = self.gru(gfeat.unsqueeze(0), gfeat_prev.unsqueeze(0))[0].squeeze(0)
+        finally:
+            self.gru.training = mode
         return torch.cat((prop.transpose(1, 2), gfeat_new.unsqueeze(2).expand(-1, -1, Nm)), dim=1), gfeat_new
 
     def forward_ragged(self, pc1, pc2, feature1, feature2, npoints1, npoints2, gfeat, validate=False):
         """CMFlow.forward_ragged with the recurrent global feature carried across the frames of a clip (clip_util.py:34-62):
         gfeat (B,256) of the previous frame or None -> (sf_agg, stat_cls, pre_trans, mask, gfeat)."""
         return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat)
+
+    def forward_ragged_train(self, pc1, pc2, feature1, feature2, npoints1, npoints2, label_m, gfeat, validate=False):
+        """CMFlow.forward_ragged_train with the recurrent global feature: gfeat (B,256) of the previous frame or None ->
+        (sf_agg, mseg_pre, pre_trans, mask, gfeat); the gradient flows through the GRU and the counted global max."""
+        return self._forward_ragged(pc1, pc2, feature1, feature2, npoints1, npoints2, validate, gfeat, label_m, True)
 
 
 def init_model(args, device="cuda"):

@@ -212,9 +212,11 @@ __global__ __launch_bounds__(CMF_WAVE) void ego_refine_fwd_kernel(
 //   H  = sum_n W_n (A_n - cA)(B_n - cB)^T,   cA = sum W_n A_n,   cB = sum W_n B_n,
 //   t  = -R cA + cB.
 // one sample: gt = the gradient w.r.t. its (4,4) transform as 12 doubles (rows of [R | t]); a, b (3,n), w (n); outputs per sample
+// (ld: stride between the three coordinate planes; -1 = n, the dense layout)
 __device__ __forceinline__ void kabsch_bwd_sample(int n, const float *a, const float *b, const float *w, const double *x, const double (&gt)[12],
-                                                  float *gA, float *gB, float *gW, int lane)
+                                                  float *gA, float *gB, float *gW, int lane, int ld = -1)
 {
+    if (ld < 0) ld = n;
     double U[9], S[3], V[9], ca[3], cb[3];
     for (int k = 0; k < 9; ++k) { U[k] = x[k]; V[k] = x[12 + k]; }
     for (int k = 0; k < 3; ++k) { S[k] = x[9 + k]; ca[k] = x[21 + k]; cb[k] = x[24 + k]; }
@@ -269,14 +271,14 @@ __device__ __forceinline__ void kabsch_bwd_sample(int n, const float *a, const f
     for (int i = lane; i < n; i += CMF_WAVE) {
         const double wi = w[i];
         double da[3], db[3], av[3], bv[3];
-        for (int k = 0; k < 3; ++k) { av[k] = a[k * n + i]; bv[k] = b[k * n + i]; da[k] = av[k] - ca[k]; db[k] = bv[k] - cb[k]; }
+        for (int k = 0; k < 3; ++k) { av[k] = a[k * ld + i]; bv[k] = b[k * ld + i]; da[k] = av[k] - ca[k]; db[k] = bv[k] - cb[k]; }
         double hb[3], ha[3];       // G_H^T da,  G_H db
         for (int k = 0; k < 3; ++k) {
             hb[k] = GH[0 * 3 + k] * da[0] + GH[1 * 3 + k] * da[1] + GH[2 * 3 + k] * da[2];
             ha[k] = GH[k * 3 + 0] * db[0] + GH[k * 3 + 1] * db[1] + GH[k * 3 + 2] * db[2];
         }
-        if (gB) for (int k = 0; k < 3; ++k) gB[k * n + i] = (float)(wi * (hb[k] + gcB[k]));
-        if (gA) for (int k = 0; k < 3; ++k) gA[k * n + i] = (float)(wi * (ha[k] + gcA[k]));
+        if (gB) for (int k = 0; k < 3; ++k) gB[k * ld + i] = (float)(wi * (hb[k] + gcB[k]));
+        if (gA) for (int k = 0; k < 3; ++k) gA[k * ld + i] = (float)(wi * (ha[k] + gcA[k]));
         if (gW) {
             double g = da[0] * ha[0] + da[1] * ha[1] + da[2] * ha[2];
             for (int k = 0; k < 3; ++k) g += gcA[k] * av[k] + gcB[k] * bv[k];
@@ -301,38 +303,51 @@ __global__ __launch_bounds__(CMF_WAVE) void kabsch_bwd_kernel(
 //   masked points: sf = R a + t - a  ->  G_R += g_sf a^T, g_t += g_sf;  the others hand g_sf to flow
 //   kabsch backward with the summed transform gradient -> g_B (= g_flow's second part: B = pc1 + flow), g_w
 //   w = s / sum(s)  ->  g_s = (g_w - sum(g_w w)) / sum(s)
+// COUNTED (cmf_ego_refine_grad_counted, ragged samples): sample bs has n = cnt[bs] <= ld points, its rows ld apart.  The masked G_R / g_t
+// sums, the Kabsch backward, the sum(g_w w) dot and the score sum run over the n rows in the same lane-strided order, so the valid
+// slices equal the dense call's on the truncated sample bit for bit; the slots behind n of g_flow, g_w and g_score are written as
+// zeros whatever g_sf holds there.  Dense: n == ld, cnt is not read.
+template <bool COUNTED>
 __global__ __launch_bounds__(CMF_WAVE) void ego_refine_bwd_kernel(
-    int n, float eps, const float *__restrict__ pc1, const float *__restrict__ score, const float *__restrict__ W, const float *__restrict__ Bm,
+    int ld, float eps, const float *__restrict__ pc1, const float *__restrict__ score, const float *__restrict__ W, const float *__restrict__ Bm,
     const unsigned char *__restrict__ mask, const double *__restrict__ aux, const float *__restrict__ g_sf, const float *__restrict__ g_trans,
-    float *__restrict__ g_flow, float *g_w, float *__restrict__ g_score)
+    float *__restrict__ g_flow, float *g_w, float *__restrict__ g_score, const int *__restrict__ cnt)
 {
     const int bs = blockIdx.x, lane = threadIdx.x;
-    const float *a = pc1 + (size_t)bs * 3 * n, *gs = g_sf + (size_t)bs * 3 * n, *w = W + (size_t)bs * n;
-    const unsigned char *mk = mask + (size_t)bs * n;
+    const int n = COUNTED ? max(0, min(cnt[bs], ld)) : ld;
+    const float *a = pc1 + (size_t)bs * 3 * ld, *gs = g_sf + (size_t)bs * 3 * ld, *w = W + (size_t)bs * ld;
+    const unsigned char *mk = mask + (size_t)bs * ld;
     double gt[12];
     for (int k = 0; k < 12; ++k) gt[k] = 0.0;
     for (int i = lane; i < n; i += CMF_WAVE) {
         if (!mk[i]) continue;
-        const double av[3] = {a[i], a[n + i], a[2 * n + i]};
+        const double av[3] = {a[i], a[ld + i], a[2 * ld + i]};
         for (int r = 0; r < 3; ++r) {
-            const double g = gs[r * n + i];
+            const double g = gs[r * ld + i];
             gt[r * 4 + 0] += g * av[0]; gt[r * 4 + 1] += g * av[1]; gt[r * 4 + 2] += g * av[2]; gt[r * 4 + 3] += g;
         }
     }
     for (int k = 0; k < 12; ++k) gt[k] = wave_sum(gt[k]) + (g_trans ? (double)g_trans[(size_t)bs * 16 + k] : 0.0);
-    float *gf = g_flow + (size_t)bs * 3 * n, *gw = g_w + (size_t)bs * n;
-    kabsch_bwd_sample(n, a, Bm + (size_t)bs * 3 * n, w, aux + (size_t)bs * KB_AUX, gt, nullptr, gf, gw, lane);
+    float *gf = g_flow + (size_t)bs * 3 * ld, *gw = g_w + (size_t)bs * ld;
+    if (COUNTED) kabsch_bwd_sample(n, a, Bm + (size_t)bs * 3 * ld, w, aux + (size_t)bs * KB_AUX, gt, nullptr, gf, gw, lane, ld);
+    else kabsch_bwd_sample(n, a, Bm + (size_t)bs * 3 * ld, w, aux + (size_t)bs * KB_AUX, gt, nullptr, gf, gw, lane);
     // (a lane re-reads only the entries it wrote itself: no barrier)
     double dot = 0.0, ssum = 0.0;
     for (int i = lane; i < n; i += CMF_WAVE) {
-        if (!mk[i]) for (int k = 0; k < 3; ++k) gf[k * n + i] += gs[k * n + i];
+        if (!mk[i]) for (int k = 0; k < 3; ++k) gf[k * ld + i] += gs[k * ld + i];
         dot += (double)gw[i] * (double)w[i];
-        ssum += (double)(score[(size_t)bs * n + i] + eps);
+        ssum += (double)(score[(size_t)bs * ld + i] + eps);
     }
+    if (COUNTED)
+        for (int i = n + lane; i < ld; i += CMF_WAVE) {            // padding of a ragged sample: zero gradient
+            gw[i] = 0.f;
+            for (int k = 0; k < 3; ++k) gf[k * ld + i] = 0.f;
+            if (g_score) g_score[(size_t)bs * ld + i] = 0.f;
+        }
     if (!g_score) return;
     dot = wave_sum(dot);
     const float tot = (float)wave_sum(ssum);
-    for (int i = lane; i < n; i += CMF_WAVE) g_score[(size_t)bs * n + i] = (float)(((double)gw[i] - dot) / (double)tot);
+    for (int i = lane; i < n; i += CMF_WAVE) g_score[(size_t)bs * ld + i] = (float)(((double)gw[i] - dot) / (double)tot);
 }
 
 extern "C" int cmf_weighted_kabsch(int b, int n, const float *A, const float *Bm, const float *W,
@@ -387,8 +402,20 @@ extern "C" int cmf_ego_refine_grad(int b, int n, float eps, const float *pc1, co
     CMF_CHECK_ARG(b >= 0 && n > 0);
     if (b == 0) return 0;
     CMF_CHECK_ARG(pc1 && score && W && Bm && mask && aux && g_sf && g_flow && g_w);
-    hipLaunchKernelGGL(ego_refine_bwd_kernel, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux, g_sf,
-                       g_trans, g_flow, g_w, g_score);
+    hipLaunchKernelGGL(ego_refine_bwd_kernel<false>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux, g_sf,
+                       g_trans, g_flow, g_w, g_score, (const int *)nullptr);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_ego_refine_grad_counted(int b, int n, float eps, const float *pc1, const float *score, const int *cnt, const float *W,
+                                           const float *Bm, const unsigned char *mask, const double *aux, const float *g_sf,
+                                           const float *g_trans, float *g_flow, float *g_w, float *g_score, void *stream)
+{
+    CMF_CHECK_ARG(b >= 0 && n > 0);
+    if (b == 0) return 0;
+    CMF_CHECK_ARG(pc1 && score && cnt && W && Bm && mask && aux && g_sf && g_flow && g_w);
+    hipLaunchKernelGGL(ego_refine_bwd_kernel<true>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux, g_sf,
+                       g_trans, g_flow, g_w, g_score, cnt);
     return cmf_launch_status();
 }
 

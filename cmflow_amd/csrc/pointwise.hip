@@ -1331,9 +1331,15 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_kernel(
     }
 }
 
+// Backward.  COUNTED (cmf_global_max_cat_grad_counted): the broadcast half is summed over the rows below the sample's count in the same
+// per-thread walk and fold, the rows below the count get dout (+ the sum at the arg row) and the rows behind it are written as zeros
+// whatever dout holds there -- valid rows equal the dense call's on the truncated sample bit for bit.  Dense: cnt is not read.
+template <bool COUNTED>
 __global__ __launch_bounds__(GM_THREADS) void global_max_cat_grad_kernel(
-    int N, int C, const float *__restrict__ dout, long long ldd, const int *__restrict__ arg, float *__restrict__ df, long long ldf)
+    int N, int C, const float *__restrict__ dout, long long ldd, const int *__restrict__ arg, float *__restrict__ df, long long ldf,
+    const int *__restrict__ cnt)
 {
+    const int Nv = COUNTED ? max(0, min(cnt[blockIdx.y], N)) : N;
     __shared__ float ssum[GM_THREADS / 16][GM_CH];
     const int b = blockIdx.y, c0 = blockIdx.x * GM_CH;
     const int tc = (threadIdx.x % 16) * 4, rg = threadIdx.x / 16;
@@ -1343,7 +1349,7 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_grad_kernel(
     float *fb = df + (long long)b * N * ldf;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     if (live)
-        for (int n = rg; n < N; n += GM_THREADS / 16) {
+        for (int n = rg; n < Nv; n += GM_THREADS / 16) {
             const float4 v = *(const float4 *)(db + (long long)n * ldd + C + c);
             s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
         }
@@ -1359,7 +1365,7 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_grad_kernel(
     if (live) {
         const int4 a = *(const int4 *)(arg + (long long)b * C + c);
         const float4 g = make_float4(ssum[0][tc], ssum[0][tc + 1], ssum[0][tc + 2], ssum[0][tc + 3]);
-        for (int n = rg; n < N; n += GM_THREADS / 16) {
+        for (int n = rg; n < Nv; n += GM_THREADS / 16) {
             float4 v = *(const float4 *)(db + (long long)n * ldd + c);
             if (n == a.x) v.x += g.x;
             if (n == a.y) v.y += g.y;
@@ -1367,6 +1373,9 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_grad_kernel(
             if (n == a.w) v.w += g.w;
             *(float4 *)(fb + (long long)n * ldf + c) = v;
         }
+        if (COUNTED)
+            for (int n = Nv + rg; n < N; n += GM_THREADS / 16)      // padded rows: zero gradient
+                *(float4 *)(fb + (long long)n * ldf + c) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 
@@ -1397,8 +1406,19 @@ extern "C" int cmf_global_max_cat_grad(int B, int N, int C, const float *dout, l
     CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldd >= 2 * C && ldf % 4 == 0 && ldd % 4 == 0 && B < 65536);
     if (B == 0) return 0;
     CMF_CHECK_ARG(dout && df && arg && (((uintptr_t)dout | (uintptr_t)df | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_grad_kernel, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout, ldd, arg,
-                       df, ldf);
+    hipLaunchKernelGGL(global_max_cat_grad_kernel<false>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout, ldd, arg,
+                       df, ldf, (const int *)nullptr);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_global_max_cat_grad_counted(int B, int N, int C, const float *dout, long long ldd, const int *arg, float *df, long long ldf,
+                                               const int *cnt, void *stream)
+{
+    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldd >= 2 * C && ldf % 4 == 0 && ldd % 4 == 0 && B < 65536);
+    if (B == 0) return 0;
+    CMF_CHECK_ARG(dout && df && arg && cnt && (((uintptr_t)dout | (uintptr_t)df | (uintptr_t)arg) & 15) == 0);
+    hipLaunchKernelGGL(global_max_cat_grad_kernel<true>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout, ldd,
+                       arg, df, ldf, cnt);
     return cmf_launch_status();
 }
 

@@ -1150,7 +1150,7 @@ class MultiScaleBlockFn(Function):
 
     @staticmethod
     def forward(ctx, xyz_t, y_all, plan, streams, sink_mode, counts, *params):
-        """counts: None, or (inference only) the (B,) int32 point counts of RAGGED samples on the device -- xyz_t / y_all are then padded
+        """counts: None, or (eval-mode BatchNorm only) the (B,) int32 point counts of RAGGED samples on the device -- xyz_t / y_all are then padded
         to N rows per sample and the blocks run behind the counted nested ball query (_multi_call): neighbours of a valid point are
         points of its own sample below its count, a padded point's neighbour is point 0 of its sample."""
         B, N, _ = xyz_t.shape
@@ -1266,13 +1266,16 @@ def set_conv_params(module):
 
 def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all, counts=None):
     """modules: the PointLocalFeature scales; y_all (B,N,len*O1) the stacked hoisted first-conv features.
-    counts ((B,) int32 on the device): RAGGED samples padded to N rows, inference only (eval-mode BatchNorm is row-wise; under
-    torch.no_grad()), N <= 1024 (the counted one-scan ball query) -- refused otherwise rather than sent down an uncounted path."""
+    counts ((B,) int32 on the device): RAGGED samples padded to N rows, eval-mode BatchNorm only (row-wise in both directions: with
+    autograd recording, the backward reuses the saved neighbour lists and needs no counts -- a padded row's gradient is zero and adds
+    +-0 wherever it is summed), N <= 1024 (the counted one-scan ball query) -- refused otherwise rather than sent down an uncounted
+    path."""
     B, N, _ = xyz_t.shape
     training = modules[0].mlp_bns[0].training
     if counts is not None:
-        if training or torch.is_grad_enabled():
-            raise RuntimeError("ragged set-conv blocks are inference only (eval-mode BatchNorm, torch.no_grad())")
+        if training:
+            raise RuntimeError("ragged set-conv blocks need eval-mode BatchNorm (batch statistics over padded rows are a different "
+                               "computation)")
         if N > 1024:
             raise ValueError("ragged batches cover clouds of up to 1024 points (the counted one-scan ball query); got Nmax = %d" % N)
     plan = _plan(encoder, modules, B, N, y_all.shape[2] // len(modules), training, xyz_t.device)
@@ -1496,9 +1499,41 @@ def global_max_cat(f):
     return GlobalMaxCatFn.apply(f)
 
 
+class GlobalMaxCatCountedFn(Function):
+    """GlobalMaxCatFn over RAGGED samples: f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows below each
+    sample's count; backward is cmf_global_max_cat_grad_counted (the broadcast half summed over the valid rows only, padded rows of
+    the gradient zero), reading a row-strided incoming gradient in place like the dense node."""
+
+    @staticmethod
+    def forward(ctx, f, counts):
+        B, N, C = f.shape
+        f = f.contiguous()
+        out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
+        arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
+        _lib.check(L().cmf_global_max_cat_counted(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.dev_ptr(counts, torch.int32),
+                                                  _lib.stream_ptr()), "cmf_global_max_cat_counted")
+        ctx.arg, ctx.counts = arg, counts
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, C = ctx.arg.shape
+        N = dout.shape[1]
+        if not (dout.stride(2) == 1 and dout.stride(0) == N * dout.stride(1) and dout.stride(1) % 4 == 0 and dout.data_ptr() % 16 == 0):
+            dout = dout.contiguous()
+        df = torch.empty(B, N, C, dtype=_f32, device=dout.device)
+        _lib.check(L().cmf_global_max_cat_grad_counted(B, N, C, dout.data_ptr(), dout.stride(1), _p(ctx.arg), _p(df), C,
+                                                       _lib.dev_ptr(ctx.counts, torch.int32), _lib.stream_ptr()),
+                   "cmf_global_max_cat_grad_counted")
+        return df, None
+
+
 def global_max_cat_counted(f, counts, want_arg=False):
-    """global_max_cat over RAGGED samples (inference): f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows
-    below each sample's count (cmf_global_max_cat_counted); want_arg: also the (B,C) int32 first row attaining it."""
+    """global_max_cat over RAGGED samples: f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows
+    below each sample's count (cmf_global_max_cat_counted); want_arg: also the (B,C) int32 first row attaining it.  With autograd
+    recording and f needing a gradient: the GlobalMaxCatCountedFn node."""
+    if torch.is_grad_enabled() and f.requires_grad and not want_arg:
+        return GlobalMaxCatCountedFn.apply(f, counts)
     B, N, C = f.shape
     f = f.contiguous()
     out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)

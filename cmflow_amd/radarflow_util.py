@@ -82,9 +82,12 @@ def knn_point_counted(nsample, xyz, new_xyz, n_src, return_dist=False):
 
 
 def ego_refine_counted(flow, pc1, score, counts, eps, thres):
-    """ego_refine over RAGGED samples (inference): flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
+    """ego_refine over RAGGED samples: flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
     (pre_trans (b,4,4), sf_agg (b,3,Nmax), mask (b,Nmax) bool, stat (b,Nmax)): the solve over each sample's valid points
-    (cmf_ego_refine_counted: bit-identical to the dense call on the truncated sample); padded slots: flow 0, mask False, stat 0."""
+    (cmf_ego_refine_counted: bit-identical to the dense call on the truncated sample); padded slots: flow 0, mask False, stat 0.
+    With autograd recording and an input that needs a gradient this is the _EgoRefineCounted node (stat carries no gradient)."""
+    if torch.is_grad_enabled() and (flow.requires_grad or score.requires_grad):
+        return _EgoRefineCounted.apply(flow, pc1, score, counts, eps, thres)
     flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
     b, _, n = pc1.shape
     dev = pc1.device
@@ -187,6 +190,49 @@ class _EgoRefine(Function):
         return g_flow, None, g_score, None, None
 
 
+class _EgoRefineCounted(Function):
+    """_EgoRefine over RAGGED samples (training under eval-mode BatchNorm): flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
+    pre_trans, sf_agg, mask, stat as ego_refine_counted returns them, with the solve's aux record kept; backward is
+    cmf_ego_refine_grad_counted -- the valid slices of the gradients equal the dense node's on the truncated sample bit for bit and
+    the padded slots are zeros whatever the incoming gradient holds there."""
+
+    @staticmethod
+    def forward(ctx, flow, pc1, score, counts, eps, thres):
+        flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
+        b, _, n = pc1.shape
+        dev = pc1.device
+        W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
+        trans = torch.empty(b, 4, 4, dtype=_f32, device=dev); aux = torch.empty(b, 32, dtype=torch.float64, device=dev)
+        sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
+        stat = torch.empty(b, n, dtype=_f32, device=dev)
+        err = _lib.lib().cmf_ego_refine_counted(b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32),
+                                                _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32),
+                                                _lib.dev_ptr(trans, _f32), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(sf, _f32),
+                                                mask.data_ptr(), _lib.dev_ptr(stat, _f32), _lib.stream_ptr())
+        _lib.check(err, "cmf_ego_refine_counted")
+        ctx.save_for_backward(pc1, score, W, Bm, mask, aux, counts)
+        ctx.eps = float(eps)
+        mask_b = mask.view(torch.bool)
+        ctx.mark_non_differentiable(mask_b, stat)
+        return trans, sf, mask_b, stat
+
+    @staticmethod
+    def backward(ctx, g_trans, g_sf, _g_mask, _g_stat):
+        pc1, score, W, Bm, mask, aux, counts = ctx.saved_tensors
+        b, _, n = pc1.shape
+        if g_sf is None:
+            g_sf = torch.zeros_like(Bm)
+        g_flow = torch.empty_like(Bm); g_w = torch.empty_like(W)
+        g_score = torch.empty_like(W) if ctx.needs_input_grad[2] else None
+        err = _lib.lib().cmf_ego_refine_grad_counted(
+            b, n, ctx.eps, _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32),
+            _lib.dev_ptr(Bm, _f32), mask.data_ptr(), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(g_sf.contiguous(), _f32),
+            _lib.dev_ptr(g_trans.contiguous(), _f32) if g_trans is not None else None,
+            _lib.dev_ptr(g_flow, _f32), _lib.dev_ptr(g_w, _f32), _lib.dev_ptr(g_score, _f32), _lib.stream_ptr())
+        _lib.check(err, "cmf_ego_refine_grad_counted")
+        return g_flow, None, g_score, None, None, None
+
+
 def ego_refine(flow, pc1, score, eps, thres):
     """-> (pre_trans, sf_agg, mask): cmflow.py:96-125 with score (b,N) the (detached label or predicted) motion scores."""
     return _EgoRefine.apply(flow, pc1, score, eps, thres)
@@ -260,13 +306,14 @@ class MultiScaleEncoder(nn.Module):
             main.wait_stream(st)
         return torch.cat(outs, dim=2)
 
-    def forward_pm_ragged(self, xyz_t, feats, counts, n_tail=0):
-        """forward_pm over RAGGED samples (inference): xyz_t (B,Nmax,3), feats (B,Nmax,C) padded, counts (B,) int32 on the device.
-        The stacked first conv is row-wise and runs on all rows; the blocks run behind the counted nested ball query."""
+    def forward_pm_ragged(self, xyz_t, feats, counts, n_tail=0, n_grad=0):
+        """forward_pm over RAGGED samples (eval-mode BatchNorm): xyz_t (B,Nmax,3), feats (B,Nmax,C) padded, counts (B,) int32 on the
+        device.  The stacked first conv is row-wise and runs on all rows; the blocks run behind the counted nested ball query.
+        n_grad: as in forward_pm (only read when autograd records the call)."""
         if not (FB.USE_BLOCK_CALLS and feats.shape[2] % 4 == 0):
             raise RuntimeError("the ragged encoder runs on the block calls (rows of a multiple of 4 floats)")
         B, N, Kp = feats.shape
-        y_all = FB.StackedFirstConvFn.apply(feats.reshape(B * N, Kp), n_tail, 0, *[sa.mlp_convs[0].weight for sa in self.ms_ls]).view(B, N, -1)
+        y_all = FB.StackedFirstConvFn.apply(feats.reshape(B * N, Kp), n_tail, n_grad, *[sa.mlp_convs[0].weight for sa in self.ms_ls]).view(B, N, -1)
         if self._streams is None:
             self._streams = FB.scale_streams(len(self.ms_ls))
         return FB.multi_scale_set_conv(self, list(self.ms_ls), self._streams, xyz_t, y_all, counts)
@@ -433,7 +480,8 @@ class FeatureCorrelator(nn.Module):
     def forward_pm(self, xyz1_t, xyz2_t, f1, f2, n1=None, n2=None):
         """Point-major cost volume.  xyz*_t (B,N,3), f1/f2 (B,N,D) -> (B,N,512).  The first conv
         over cat[f1, f2[idx], dxyz] is split by linearity into per-point GEMMs.
-        n1, n2 ((B,) int32, inference): ragged samples -- both neighbour searches take candidates below the sample's count only."""
+        n1, n2 ((B,) int32): ragged samples -- both neighbour searches take candidates below the sample's count only (they produce
+        indices: under autograd the same nodes record as in the dense call)."""
         assert not self.bn
         return self._forward_blocks(xyz1_t, xyz2_t, f1, f2, n1, n2)
 

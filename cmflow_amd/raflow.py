@@ -71,3 +71,8 @@ class RaFlow(CMFlow):
         votes over all points of a sample; a counted form of it is a different piece of work from CMFlow's (cmflow.CMFlow.forward_ragged)."""
         raise NotImplementedError("RaFlow has no ragged-batch forward: its SFR module normalises by the padded point count; "
                                   "run RaFlow one frame pair per call (forward at B = 1)")
+
+    def forward_ragged_train(self, *args, **kwargs):
+        """Not provided, for the reason forward_ragged gives."""
+        raise NotImplementedError("RaFlow has no ragged-batch forward: its SFR module normalises by the padded point count; "
+                                  "run RaFlow one frame pair per call (forward at B = 1)")

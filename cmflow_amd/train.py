@@ -13,7 +13,7 @@ import torch
 from . import synth
 from .dp import FlatAdam, FlatGradBucket, SegmentedReducer
 from .fused_blocks import join_side_streams
-from .losses import RadarFlowLoss, make_labels
+from .losses import RadarFlowLoss, make_labels, make_labels_ragged
 
 
 class TrainStep:
@@ -99,5 +99,42 @@ class TrainStep:
             self.reducer.finish()
         else:
             self.bucket.all_reduce_mean(force=self.force_allreduce)
+        self.opt.step()
+        return loss.detach(), items, outs, labels
+
+    # ---- whole frames of their own sizes (dataset.collate_ragged / as_batch_dict_ragged) -------------------------------------------
+    def forward_loss_ragged(self, batch, validate=False):
+        """forward_loss on a RAGGED batch (``dataset.as_batch_dict_ragged``: padded tensors plus ``n1``, ``n2``):
+        make_labels_ragged -> forward_ragged_train -> RadarFlowLoss.forward_ragged.  The network must be in eval mode (BatchNorm on
+        its running statistics while gradients flow -- the reference's regime after its first epoch); the loss is the mean of the
+        per-frame totals (the reference's protocol at batch size 1).  -> (loss, items, outs, labels) as forward_loss, with
+        ``items["per_sample"]`` the (B,9) per-frame values (column 0 the total, then losses.ITEM_KEYS)."""
+        if self.self_supervised:
+            raise NotImplementedError("RaFlow has no ragged-batch training step: its SFR module normalises by the padded point count")
+        pc1, pc2, ft1, ft2, n1, n2 = (batch[k] for k in ("pc1", "pc2", "ft1", "ft2", "n1", "n2"))
+        if self.net.training:
+            raise RuntimeError("step_ragged needs eval-mode BatchNorm: call net.eval() first (train-mode batch statistics over padded "
+                               "rows are a different computation)")
+        dyn_mask, mseg_gt = make_labels_ragged(batch, self.vr_thres)
+        if self.recurrent:
+            g = self.gfeat.detach() if self.gfeat is not None else None          # clip_util.py:54
+            pred_f, mseg_pre, pre_trans, mask, self.gfeat = self.net.forward_ragged_train(pc1, pc2, ft1, ft2, n1, n2, mseg_gt, g,
+                                                                                          validate=validate)
+        else:
+            pred_f, mseg_pre, pre_trans, mask = self.net.forward_ragged_train(pc1, pc2, ft1, ft2, n1, n2, mseg_gt, validate=validate)
+        loss, items, per_sample = self.loss_obj.forward_ragged(pc1, pc2, pred_f, ft1[:, 0], n1, n2, batch["flow_label"].transpose(2, 1),
+                                                               pre_trans, mseg_pre, batch["gt_trans"], mseg_gt, dyn_mask,
+                                                               batch["radar_u"], batch["radar_v"], batch["opt_flow"], validate=validate)
+        items = dict(items, per_sample=per_sample)
+        return loss, items, (pred_f, mseg_pre, pre_trans, mask), (dyn_mask, mseg_gt)
+
+    def step_ragged(self, batch, validate=False):
+        """One optimizer step on a ragged batch: forward_loss_ragged -> zero the bucket -> backward -> join the side streams ->
+        all-reduce -> Adam.  Returns what __call__ returns."""
+        loss, items, outs, labels = self.forward_loss_ragged(batch, validate)
+        self.bucket.zero()
+        loss.backward()
+        join_side_streams()                         # gradient sinks written on side streams (fused_blocks.grad_sink)
+        self.bucket.all_reduce_mean(force=self.force_allreduce)
         self.opt.step()
         return loss.detach(), items, outs, labels

@@ -664,7 +664,18 @@ int cmf_debug_spin(float microseconds, void *stream);
  * cmf_eval_metrics_counted: per sample the 14 metrics of cmf_eval_metrics(b = 1, n = cnt[s]) on its valid rows, then their mean over
  *   the samples in index order -- what main_util.py:176-192 accumulates with the test loader's batch size 1.  A sample without
  *   static points gives stat_rne = NaN (0 / 0, numpy's mean of an empty selection) and so does the mean; a sample without moving
- *   points gives mov_rne = 0 (0 / 1e-6): both exactly as cmf_eval_metrics at b = 1.  workspace: 16 * B doubles. */
+ *   points gives mov_rne = 0 (0 / 1e-6): both exactly as cmf_eval_metrics at b = 1.  workspace: 16 * B doubles.
+ *
+ * Training on ragged batches (eval-mode BatchNorm): every layer is row-wise in both directions, so a padded row carries an exactly
+ * zero gradient and a valid row never reads a padded one; the two places where gradients fan in over a sample have counted forms that
+ * make this hold by construction, whatever the incoming gradient holds behind a sample's count:
+ * cmf_ego_refine_grad_counted: cmf_ego_refine_grad with rows n apart and every sum (masked G_R / g_t, the Kabsch backward, sum g_w w,
+ *   the score sum) over the rows < cnt[s] in the dense kernel's order: the valid slices of g_flow, g_w, g_score are bit-identical to
+ *   cmf_ego_refine_grad(b = 1, n = cnt[s]) on the truncated sample; their padded slots are zeros.  W, Bm, mask, aux: as
+ *   cmf_ego_refine_counted wrote them (aux is required).
+ * cmf_global_max_cat_grad_counted: df[s,n,c] = dout[s,n,c] + (n == arg[s,c]) * sum_{n' < cnt[s]} dout[s,n',C+c] for n < cnt[s], bit-
+ *   identical to cmf_global_max_cat_grad(B = 1, N = cnt[s]) on the truncated sample; the rows behind the count are zeros.  dout may
+ *   be row-strided (ldd) as in the dense call. */
 int cmf_ball_query_multi_counted(int b, int n, int m, int nq, const float *radii, const int *nsamples, int nclouds,
                                  const float *const *new_xyz, const float *const *xyz, int *const *idx,
                                  const int *const *n_ctr, const int *const *n_src, void *stream);
@@ -679,6 +690,11 @@ int cmf_ego_refine_counted(int b, int n, float eps, float thres, const float *pc
 int cmf_eval_metrics_counted(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
                              const float *pred_m, const float *gt_trans, const float *pred_trans,
                              float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream);
+int cmf_ego_refine_grad_counted(int b, int n, float eps, const float *pc1, const float *score, const int *cnt, const float *W,
+                                const float *Bm, const unsigned char *mask, const double *aux, const float *g_sf,
+                                const float *g_trans, float *g_flow, float *g_w, float *g_score, void *stream);
+int cmf_global_max_cat_grad_counted(int B, int N, int C, const float *dout, long long ldd, const int *arg, float *df, long long ldf,
+                                    const int *cnt, void *stream);
 
 /* ---- ragged batches: the loss and the pseudo labels on whole frames ---------------------------------------------------------
  * cmf_radar_loss_counted: cmf_radar_loss on B padded samples of their own sizes.  Everything indexed by the points of cloud 1 (pc1,

@@ -1,0 +1,498 @@
+"""GPU: training on ragged batches under eval-mode BatchNorm -- CMFlow.forward_ragged_train, TrainStep.step_ragged and the two counted
+backward kernels (cmf_ego_refine_grad_counted, cmf_global_max_cat_grad_counted).
+
+Yardsticks are never the ragged path itself: the DENSE entry points at B = 1 on the truncated sample (bit-exact claims) and the CPU
+oracle at B = 1 on the truncated sample (the reference gradient of a ragged step is the mean over the samples of the oracle's eval-mode
+gradients, in fp32 and fp64: tests/ragged_train_case.py).  Gradient bounds: the larger of the project's defaults and 3 x the oracle's
+own fp32-vs-fp64 floor for exactly these mean gradients (tests/ragged_train_grad_floor.py, profiles/ragged_train_grad_floor.txt)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import ragged_loss_case as RC
+import ragged_train_case as TC
+from cmflow_amd import synth
+from cmflow_amd.losses import ITEM_KEYS, make_labels_ragged
+from test_gpu_ragged import _check_against
+
+pytestmark = pytest.mark.gpu
+_f32, _i32 = torch.float32, torch.int32
+NMAX = 300
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    return torch.device("cuda:0")
+
+
+def _to(d, dev):
+    return {k: v.to(dev) for k, v in d.items()}
+
+
+def _garbage(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return 1e4 * (torch.randint(0, 2, shape, generator=g) * 2 - 1).float()
+
+
+def _pad_last(t, counts, seed):
+    """t (B,...,NMAX): slots behind counts[i] along the LAST axis overwritten with +-1e4."""
+    out = t.clone()
+    junk = _garbage(t.shape, seed)
+    for i, c in enumerate(counts):
+        out[i, ..., c:] = junk[i, ..., c:]
+    return out
+
+
+# ---- 1. the kernels ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("eps", [1e-4, 0.0])
+@pytest.mark.parametrize("with_score_grad", [True, False])
+def test_counted_ego_refine_grad_is_bit_exact(dev, eps, with_score_grad):
+    """Every sample of COUNTS6, padded slots of every input and of both incoming gradients +-1e4: g_flow, g_w, g_score on [:cnt] ==
+    cmf_ego_refine_grad at b = 1 on the truncated sample, padded slots of all three 0."""
+    from cmflow_amd import _lib
+    L, p = _lib.lib(), _lib.dev_ptr
+    counts = [c[0] for c in RC.COUNTS6]
+    B = len(counts)
+    b = synth.make_batch(B, NMAX, seed=21)
+    g = torch.Generator().manual_seed(3)
+    pc1 = _pad_last(b["pc1"], counts, 1).to(dev)
+    flow = _pad_last(0.3 * torch.randn(B, 3, NMAX, generator=g), counts, 2).to(dev)
+    score = _pad_last(torch.rand(B, NMAX, generator=g), counts, 3).to(dev)
+    g_sf = _pad_last(torch.randn(B, 3, NMAX, generator=g), counts, 4).to(dev)
+    g_tr = torch.randn(B, 4, 4, generator=g).to(dev)
+    cnt = torch.tensor(counts, dtype=_i32, device=dev)
+
+    def buffers(bb, n):
+        z = lambda *s, dt=_f32: torch.full(s, -7.0, dtype=dt, device=dev) if dt == _f32 else torch.zeros(s, dtype=dt, device=dev)
+        return dict(W=z(bb, n), Bm=z(bb, 3, n), trans=z(bb, 4, 4), aux=z(bb, 32, dt=torch.float64), sf=z(bb, 3, n),
+                    mask=z(bb, n, dt=torch.uint8), g_flow=z(bb, 3, n), g_w=z(bb, n), g_score=z(bb, n) if with_score_grad else None)
+
+    r = buffers(B, NMAX)
+    stat = torch.empty(B, NMAX, device=dev)
+    _lib.check(L.cmf_ego_refine_counted(B, NMAX, eps, 0.5, p(pc1, _f32), p(flow, _f32), p(score, _f32), p(cnt, _i32), p(r["W"], _f32),
+                                        p(r["Bm"], _f32), p(r["trans"], _f32), p(r["aux"], torch.float64), p(r["sf"], _f32),
+                                        r["mask"].data_ptr(), p(stat, _f32), _lib.stream_ptr()), "fwd counted")
+    _lib.check(L.cmf_ego_refine_grad_counted(B, NMAX, eps, p(pc1, _f32), p(score, _f32), p(cnt, _i32), p(r["W"], _f32), p(r["Bm"], _f32),
+                                             r["mask"].data_ptr(), p(r["aux"], torch.float64), p(g_sf, _f32), p(g_tr, _f32),
+                                             p(r["g_flow"], _f32), p(r["g_w"], _f32), p(r["g_score"], _f32), _lib.stream_ptr()), "bwd counted")
+    for i, n in enumerate(counts):
+        c = lambda t: t[i:i + 1, ..., :n].contiguous()
+        d = buffers(1, n)
+        a, f, s, gs, gt = c(pc1), c(flow), c(score), c(g_sf), g_tr[i:i + 1].contiguous()
+        _lib.check(L.cmf_ego_refine(1, n, eps, 0.5, p(a, _f32), p(f, _f32), p(s, _f32), p(d["W"], _f32), p(d["Bm"], _f32), p(d["trans"], _f32),
+                                    p(d["aux"], torch.float64), p(d["sf"], _f32), d["mask"].data_ptr(), _lib.stream_ptr()), "fwd dense")
+        _lib.check(L.cmf_ego_refine_grad(1, n, eps, p(a, _f32), p(s, _f32), p(d["W"], _f32), p(d["Bm"], _f32), d["mask"].data_ptr(),
+                                         p(d["aux"], torch.float64), p(gs, _f32), p(gt, _f32), p(d["g_flow"], _f32), p(d["g_w"], _f32),
+                                         p(d["g_score"], _f32), _lib.stream_ptr()), "bwd dense")
+        assert 0 < int(d["mask"].sum()) < n, (i, "both branches of the select")
+        for k in ("g_flow", "g_w", "g_score"):
+            if r[k] is None:
+                continue
+            assert torch.equal(r[k][i, ..., :n].view(_i32), d[k][0].view(_i32)), (k, i, n)
+            assert not r[k][i, ..., n:].any(), (k, i, n)
+            assert torch.isfinite(d[k]).all() and d[k].any(), (k, i)
+
+
+@pytest.mark.parametrize("strided", [False, True])
+def test_counted_global_max_grad_is_bit_exact(dev, strided):
+    """df on [:cnt] == cmf_global_max_cat_grad at B = 1 on the truncated sample; padded rows of df 0 although dout holds +-1e4 there.
+    strided: dout is a 512-column block of a 1040-wide tensor, read in place."""
+    from cmflow_amd import fused_blocks as FB
+    counts = [c[0] for c in RC.COUNTS6]
+    B, C = len(counts), 256
+    g = torch.Generator().manual_seed(5)
+    f = torch.randn(B, NMAX, C, generator=g)
+    f[:, :, 3] = 0.25                                                # a channel of ties: arg = the first row
+    junk = _garbage((B, NMAX, C), 1)
+    for i, n in enumerate(counts):
+        f[i, n:] = junk[i, n:]
+    f = f.to(dev)
+    cnt = torch.tensor(counts, dtype=_i32, device=dev)
+    _, arg = FB.global_max_cat_counted(f, cnt, want_arg=True)
+    wide = torch.randn(B, NMAX, 1040, generator=g)
+    junk = _garbage((B, NMAX, 1040), 2)
+    for i, n in enumerate(counts):
+        wide[i, n:] = junk[i, n:]
+    wide = wide.to(dev)
+    dout = wide[:, :, :2 * C] if strided else wide[:, :, :2 * C].contiguous()
+    df = torch.full((B, NMAX, C), -7.0, device=dev)
+    FB._lib.check(FB.L().cmf_global_max_cat_grad_counted(B, NMAX, C, dout.data_ptr(), dout.stride(1), arg.data_ptr(), df.data_ptr(), C,
+                                                         cnt.data_ptr(), FB._lib.stream_ptr()), "counted")
+    for i, n in enumerate(counts):
+        di = wide[i:i + 1, :n, :2 * C] if strided else wide[i:i + 1, :n, :2 * C].contiguous()
+        want = torch.full((1, n, C), -7.0, device=dev)
+        FB._lib.check(FB.L().cmf_global_max_cat_grad(1, n, C, di.data_ptr(), di.stride(1), arg[i:i + 1].contiguous().data_ptr(),
+                                                     want.data_ptr(), C, FB._lib.stream_ptr()), "dense")
+        assert torch.equal(df[i, :n].view(_i32), want[0].view(_i32)), i
+        assert not df[i, n:].any(), i
+    # ... and through the autograd node, on the gradient of a consumer that reads the padded rows too
+    x = f.clone().requires_grad_(True)
+    out = FB.global_max_cat_counted(x, cnt)
+    assert type(out.grad_fn).__name__.startswith("GlobalMaxCatCountedFn")
+    out.backward(wide[:, :, :2 * C])
+    assert torch.equal(x.grad, df)
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------------------
+def _net(dev, t=False):
+    from cmflow_amd.cmflow import CMFlow, CMFlow_T
+    net = (CMFlow_T if t else CMFlow)(TC.Args())
+    net.load_state_dict(TC.weights(t))
+    return net.to(dev).eval()
+
+
+def _grads(net):
+    return {k: (p.grad.detach().clone() if p.grad is not None else None) for k, p in net.named_parameters()}
+
+
+def _ragged_gradient(step, pb, dev):
+    """One forward_loss_ragged + backward into the zeroed bucket -> loss, items, outs, flat bucket copy."""
+    from cmflow_amd.fused_blocks import join_side_streams
+    loss, items, outs, labels = step.forward_loss_ragged(_to(pb, dev), validate=True)
+    step.bucket.zero()
+    loss.backward()
+    join_side_streams()
+    torch.cuda.synchronize()
+    return loss.detach(), items, outs, step.bucket.flat.clone()
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, dtype):
+    counts, seed = TC.CASES[case]
+    return TC.oracle_mean_gradient(TC.weights(), RC.make_case(counts, seed)[0], counts, dtype)
+
+
+def _dense_single(net, b, label, dev):
+    return net(*(b[k].to(dev) for k in ("pc1", "pc2", "ft1", "ft2")), label, "train")
+
+
+@pytest.mark.parametrize("case", list(TC.CASES))
+def test_forward_ragged_train_matches_the_dense_train_forward_per_sample(dev, case):
+    """2. With autograd recording, against the dense eval-mode forward(..., label_m, 'train') at B = 1 on every truncated sample
+    (N1 != N2 included), the comparison and bounds tests/test_gpu_ragged.py applies to forward_ragged; padded output slots zero;
+    under no_grad with label_m = None the result is forward_ragged's, bit for bit."""
+    counts, seed = TC.CASES[case]
+    net = _net(dev)
+    batch = RC.make_case(counts, seed)[0]
+    pb = _to(TC.padded(batch, counts, 300, 256), dev)
+    _, mseg = make_labels_ragged(pb, 0.3)
+    assert torch.is_grad_enabled()
+    got = net.forward_ragged_train(pb["pc1"], pb["pc2"], pb["ft1"], pb["ft2"], pb["n1"], pb["n2"], mseg, validate=True)
+    assert got[0].requires_grad and got[1].requires_grad and got[2].requires_grad and got[3].dtype == torch.bool
+    assert got[0].shape == (len(counts), 3, 300) and got[1].shape == (len(counts), 1, 300) and got[3].shape == (len(counts), 300)
+    got_d = tuple(t.detach() for t in got)
+    for i, (n1, n2) in enumerate(counts):
+        b = TC.truncated(batch, counts, i)
+        with torch.no_grad():
+            want = _dense_single(net, b, mseg[i:i + 1, :n1].contiguous(), dev)
+        flips = _check_against(got_d, i, n1, want, "dense B=1 train forward")
+        assert flips == 0                                            # the mask comes from the label on both sides
+        assert not got_d[0][i, :, n1:].any() and not got_d[1][i, :, n1:].any() and not got_d[3][i, n1:].any(), i
+    assert all(torch.isfinite(t).all() for t in got_d[:3])
+    with torch.no_grad():
+        a = net.forward_ragged_train(pb["pc1"], pb["pc2"], pb["ft1"], pb["ft2"], pb["n1"], pb["n2"], None)
+        w = net.forward_ragged(pb["pc1"], pb["pc2"], pb["ft1"], pb["ft2"], pb["n1"], pb["n2"])
+    assert len(a) == len(w) == 4 and all(torch.equal(x, y) for x, y in zip(a, w))
+
+
+def test_b1_unpadded_step_gradient_equals_the_dense_eval_bn_gradient(dev):
+    """3. B = 1, n1 = n2 = Nmax = 256: the gradient bucket of the ragged step against the dense eval-BN TrainStep's on the same sample.
+    The neighbour lists, the Kabsch sums and the B = 1 loss are the same and every GEMM sees the same M: bit-identical."""
+    from cmflow_amd.fused_blocks import join_side_streams
+    from cmflow_amd.train import TrainStep
+    net = _net(dev)
+    step = TrainStep(net, vr_thres=0.3)
+    batch = RC.make_case(((256, 256),), RC.SEED6)[0]
+    b = TC.truncated(batch, ((256, 256),), 0)
+    loss_d, _, outs_d, _ = step.forward_loss(_to(b, dev))
+    step.bucket.zero()
+    loss_d.backward()
+    join_side_streams()
+    torch.cuda.synchronize()
+    dense = step.bucket.flat.clone()
+    pb = dict(b, n1=torch.tensor([256], dtype=_i32), n2=torch.tensor([256], dtype=_i32))
+    loss_r, _, outs_r, ragged = _ragged_gradient(step, pb, dev)
+    d = (ragged - dense).abs().max().item()
+    print("B = 1 unpadded: loss %.9g vs %.9g, |grad| max %.3g, max |difference| %.3g, differing elements %d of %d"
+          % (loss_r.item(), loss_d.item(), dense.abs().max().item(), d, int((ragged != dense).sum()), dense.numel()))
+    assert dense.any()
+    assert torch.equal(outs_r[0], outs_d[0]) and torch.equal(outs_r[2], outs_d[2])
+    assert torch.equal(loss_r, loss_d.detach())
+    assert torch.equal(ragged, dense)
+
+
+def _check_loss_items(per, totals, items):
+    """The bounds of test_counted_loss_matches_oracle_per_sample: 1e-4 * max(1, |ref|)."""
+    for i, (t, it) in enumerate(zip(totals, items)):
+        got = per[i].tolist()
+        assert abs(got[0] - t) < 1e-4 * max(1.0, abs(t)), (i, got[0], t)
+        for j, k in enumerate(ITEM_KEYS):
+            assert abs(got[1 + j] - it[k]) < 1e-4 * max(1.0, abs(it[k])), (i, k, got[1 + j], it[k])
+
+
+@pytest.mark.parametrize("case", list(TC.CASES))
+def test_ragged_step_gradient_matches_the_oracle_mean(dev, case):
+    """4. Padded size 300 / 256, padding +-1e4: every parameter gradient (norm, 1 - cos, largest element) and the gradient as one
+    vector against the mean of the oracle's B = 1 eval-mode gradients, fp32 and fp64; loss and items per sample against the oracle.
+    Printed without a tighter assertion: the distance to the mean of the dense GPU B = 1 gradients."""
+    from cmflow_amd.fused_blocks import join_side_streams
+    from cmflow_amd.train import TrainStep
+    counts, seed = TC.CASES[case]
+    B = len(counts)
+    net = _net(dev)
+    step = TrainStep(net, vr_thres=0.3)
+    batch = RC.make_case(counts, seed)[0]
+    loss, items, outs, flat = _ragged_gradient(step, TC.padded(batch, counts, 300, 256), dev)
+    got = _grads(net)
+    g32, totals, ref_items, _ = _reference(case, torch.float32)
+    g64 = _reference(case, torch.float64)[0]
+    print("%s: loss %.7g, oracle mean of totals %.7g" % (case, loss.item(), float(np.mean(totals))))
+    n32 = TC.check_gradients(got, g32, "%s ragged step vs oracle fp32 mean" % case, *TC.bounds_for(case, ref_dtype=torch.float32))
+    n64 = TC.check_gradients(got, g64, "%s ragged step vs oracle fp64 mean" % case, *TC.bounds_for(case))
+    assert n32 == n64 >= 180
+    _check_loss_items(items["per_sample"].cpu(), totals, ref_items)
+    assert abs(loss.item() - float(np.mean(totals))) < 1e-4 * max(1.0, abs(float(np.mean(totals))))
+    for i, (n1, _) in enumerate(counts):
+        assert not outs[0][i, :, n1:].any() and not outs[1][i, :, n1:].any(), i
+    # the mean of the dense GPU B = 1 gradients (different GEMM tiles per M: close, not equal)
+    acc = torch.zeros_like(flat)
+    from cmflow_amd.losses import make_labels
+    for i, (n1, n2) in enumerate(counts):
+        # the dense network at B = 1 on the truncated sample; its loss through the counted kernel at B = 1 (the dense loss kernel takes
+        # one N for both clouds)
+        b = _to(TC.truncated(batch, counts, i), dev)
+        dyn, mseg = make_labels(b, 0.3)
+        o = net(b["pc1"], b["pc2"], b["ft1"], b["ft2"], mseg, "train")
+        c1, c2 = torch.tensor([n1], dtype=_i32, device=dev), torch.tensor([n2], dtype=_i32, device=dev)
+        l = step.loss_obj.forward_ragged(b["pc1"], b["pc2"], o[0], b["ft1"][:, 0], c1, c2, b["flow_label"].transpose(2, 1), o[2], o[1],
+                                         b["gt_trans"], mseg, dyn, b["radar_u"], b["radar_v"], b["opt_flow"], validate=True)[0]
+        step.bucket.zero()
+        l.backward()
+        join_side_streams()
+        acc += step.bucket.flat / B
+    rel = float((flat - acc).norm() / acc.norm())
+    cos = 1.0 - float(flat.double() @ acc.double()) / float(flat.double().norm() * acc.double().norm())
+    print("%s: ragged step vs mean of dense GPU B = 1 gradients: relative error %.3g, 1 - cos %.3g" % (case, rel, cos))
+
+
+def test_padding_does_not_leak_into_the_gradient(dev):
+    """5. Same Nmax, padding of inputs and labels zeros vs +-1e4: the flat gradient bucket bit-identical (a difference means some
+    kernel lets a padded row contribute).  Nmax 384 / 320 instead of 300 / 256: within the bounds of check 4 against the oracle."""
+    from cmflow_amd.train import TrainStep
+    case = "counts6"
+    counts, seed = TC.CASES[case]
+    net = _net(dev)
+    step = TrainStep(net, vr_thres=0.3)
+    batch = RC.make_case(counts, seed)[0]
+    la, _, _, a = _ragged_gradient(step, TC.padded(batch, counts, 300, 256, "big"), dev)
+    lz, _, _, z = _ragged_gradient(step, TC.padded(batch, counts, 300, 256, "zeros"), dev)
+    lb, _, _, b2 = _ragged_gradient(step, TC.padded(batch, counts, 300, 256, "big", fill_seed=5), dev)
+    print("zeros vs +-1e4 padding: differing elements %d of %d, max |difference| %.3g; other +-1e4 pattern: %d"
+          % (int((a != z).sum()), a.numel(), (a - z).abs().max().item(), int((a != b2).sum())))
+    assert a.any() and torch.isfinite(a).all()
+    assert torch.equal(la, lz) and torch.equal(a, z)
+    assert torch.equal(la, lb) and torch.equal(a, b2)
+    _ragged_gradient(step, TC.padded(batch, counts, 384, 320, "big", fill_seed=1), dev)
+    TC.check_gradients(_grads(net), _reference(case, torch.float64)[0], "padded to 384 / 320 vs oracle fp64 mean", *TC.bounds_for(case))
+    TC.check_gradients(_grads(net), _reference(case, torch.float32)[0], "padded to 384 / 320 vs oracle fp32 mean",
+                       *TC.bounds_for(case, ref_dtype=torch.float32))
+
+
+def _oracle_adam(grads):
+    """The oracle's Adam (main.py:107: lr 1e-3, weight decay 1e-4), one step from the test weights on the given gradients."""
+    from oracle import cmflow_oracle as O
+    ref = O.CMFlow(TC.Args())
+    ref.load_state_dict(TC.weights())
+    params = []
+    for k, p in ref.named_parameters():
+        if grads[k] is not None:
+            p.grad = grads[k].float().view_as(p)
+            params.append(p)
+    torch.optim.Adam(params, lr=0.001, weight_decay=1e-4).step()
+    return {k: p.detach() for k, p in ref.named_parameters()}
+
+
+def _over(a, r):
+    """Elements of a outside atol 1e-4 + rtol 1e-3 |r| of r (the golden train-step test's bound)."""
+    return (a - r).abs() > 1e-4 + 1e-3 * r.abs()
+
+
+def test_step_ragged_updates_like_the_oracle_adam(dev):
+    """6. After one step_ragged, the parameters against the oracle's Adam (lr 1e-3, weight decay 1e-4) applied to the reference mean
+    gradient (fp32), bound rtol 1e-3 / atol 1e-4; no BN buffer moves; a second step runs.
+
+    (a) In the form of the golden train-step test, whose bound this is: the first 64 elements of EVERY parameter tensor, no exceptions.
+    (b) Every element of every tensor whose reference update cannot change sign within the gradient bound of check 4, no exceptions.
+        Adam's first step is lr * u / (|u| + 1e-8) with u = g + 1e-4 w: a sign, +-lr.  Check 4 holds every element of a tensor's
+        gradient to e * max|g_ref| of the reference (e: the element bound of TC.bounds_for); an element with
+        |u_ref| > e * max|g_ref| + 1e-7 (1e-7 = 10 x Adam's eps: beyond it the step is +-lr to within lr / 10 < atol whatever |u|)
+        therefore has the same sign in any evaluation that passes check 4 and lands within the bound.
+    Printed, not asserted: how many of ALL elements sit outside the bound (each by 2 lr: the sign of a noise-level u), and the same
+    count between the oracle's own Adam on its fp32 and on its fp64 mean gradient."""
+    from cmflow_amd.train import TrainStep
+    case = "counts6"
+    counts, seed = TC.CASES[case]
+    net = _net(dev)
+    before = {k: v.clone() for k, v in net.state_dict().items() if "running_" in k or "num_batches" in k}
+    w0 = {k: p.detach().cpu().clone() for k, p in net.named_parameters()}
+    step = TrainStep(net, vr_thres=0.3)
+    pb = _to(TC.padded(RC.make_case(counts, seed)[0], counts, 300, 256), dev)
+    loss, items, outs, labels = step.step_ragged(pb, validate=True)
+    assert torch.isfinite(loss) and items["per_sample"].shape == (len(counts), 9) and set(ITEM_KEYS) <= set(items)
+    g32 = _reference(case, torch.float32)[0]
+    a32, a64 = _oracle_adam(g32), _oracle_adam(_reference(case, torch.float64)[0])
+    have = {k: p.detach().cpu() for k, p in net.named_parameters()}
+    e = TC.bounds_for(case, ref_dtype=torch.float32)[0][2]
+    total = sum(v.numel() for v in a32.values())
+    n_self = sum(int(_over(a32[k], a64[k]).sum()) for k in a32)
+    n_all = sum(int(_over(have[k], a32[k]).sum()) for k in a32)
+    first64 = {k: int(_over(have[k].reshape(-1)[:64], a32[k].reshape(-1)[:64]).sum()) for k in a32}
+    n_held, bad_held = 0, []
+    for k, r in a32.items():
+        if g32[k] is None:
+            assert torch.equal(have[k], w0[k]), k
+            continue
+        u = g32[k].float().view_as(r) + 1e-4 * w0[k]
+        held = u.abs() > e * max(float(g32[k].abs().max()), 1e-6) + 1e-7
+        n_held += int(held.sum())
+        over = _over(have[k], r) & held
+        if over.any():
+            bad_held.append((k, int(over.sum()), float((have[k] - r).abs()[over].max())))
+    print("after one step_ragged: %d parameter elements in %d tensors; outside atol 1e-4 + rtol 1e-3 |ref|: %d of all elements (the oracle's "
+          "fp32 against its fp64 Adam: %d), %d of the first 64 of every tensor, %d of the %d elements whose sign the gradient bound fixes"
+          % (total, len(a32), n_all, n_self, sum(first64.values()), sum(n for _, n, _ in bad_held), n_held))
+    assert total > 4000000 and n_held > 200000                      # the oracle's gradient alone decides it: 226 818 on the CPU
+    for k, r in a32.items():
+        np.testing.assert_allclose(have[k].reshape(-1)[:64].numpy(), r.reshape(-1)[:64].numpy(), rtol=1e-3, atol=1e-4, err_msg=k)
+    assert not bad_held, bad_held
+    sd = net.state_dict()
+    assert all(torch.equal(sd[k], v) for k, v in before.items())
+    loss2, _, _, _ = step.step_ragged(pb)
+    assert torch.isfinite(loss2)
+
+
+def test_cmflow_t_ragged_clip_gradient_reaches_the_gru_and_the_first_frame(dev):
+    """7. CMFlow-T, a two-frame ragged clip with the recurrent feature handed over undetached: the second frame's loss reaches the GRU
+    and, through gfeat (a non-zero gradient arrives at the first frame's gfeat), the first frame's parameters; the gradient of
+    frame 1 + frame 2 against the oracle's per-sample mean (fp32 and fp64) with the second-frame allowance of the dense clip test.
+    The loss is held to the fp32 oracle only, as in check 4: the oracle's own fp32 and fp64 totals of sample 1 are 14.699 and 14.327
+    (profiles/ragged_train_grad_floor.txt: a motion-head score saturates in fp32 and the BCE clamps), 1.7e-3 of the clip's mean."""
+    from cmflow_amd.fused_blocks import join_side_streams
+    from cmflow_amd.train import TrainStep
+    counts = RC.COUNTS5
+    net = _net(dev, t=True)
+    step = TrainStep(net, vr_thres=0.3)
+    f1 = _to(TC.padded(RC.make_case(counts, RC.SEED5)[0], counts, 300, 256), dev)
+    f2 = _to(TC.padded(RC.make_case(counts, TC.SEED_T2)[0], counts, 300, 256, fill_seed=2), dev)
+
+    def frame(pb, g):
+        dyn, mseg = make_labels_ragged(pb, 0.3)
+        o = net.forward_ragged_train(pb["pc1"], pb["pc2"], pb["ft1"], pb["ft2"], pb["n1"], pb["n2"], mseg, g, validate=True)
+        total, items, per = step.loss_obj.forward_ragged(pb["pc1"], pb["pc2"], o[0], pb["ft1"][:, 0], pb["n1"], pb["n2"],
+                                                         pb["flow_label"].transpose(2, 1), o[2], o[1], pb["gt_trans"], mseg, dyn,
+                                                         pb["radar_u"], pb["radar_v"], pb["opt_flow"], validate=True)
+        return total, o
+
+    l1, o1 = frame(f1, None)
+    assert o1[4].requires_grad and o1[4].shape == (len(counts), 256)
+    l2, o2 = frame(f2, o1[4])
+    seen = []
+    o1[4].register_hook(lambda g: seen.append(g.detach().clone()))   # what the second frame hands back to the first through gfeat
+    step.bucket.zero()
+    (l1 + l2).backward()
+    join_side_streams()
+    torch.cuda.synchronize()
+    assert len(seen) == 1 and seen[0].shape == o1[4].shape and torch.isfinite(seen[0]).all() and seen[0].any()
+    got = _grads(net)
+    sd = TC.weights(True)
+    b1, b2 = RC.make_case(counts, RC.SEED5)[0], RC.make_case(counts, TC.SEED_T2)[0]
+    bounds, whole = TC.bounds_for("clip_t", TC.SECOND_FRAME_BOUNDS)
+    loose = (TC.SECOND_FRAME_MP[0], tuple(max(a, b) for a, b in zip(TC.SECOND_FRAME_MP[1], bounds)))
+    assert all(got[k].any() for k in ("gru.weight_ih_l0", "gru.weight_hh_l0", "mse_layer.ms_ls.0.mlp_convs.0.weight"))
+    for dt in (torch.float32, torch.float64):
+        ref, totals, _, _ = TC.oracle_mean_gradient(sd, b1, counts, dt, t=True, batch2=b2)
+        print("CMFlow-T clip %s: loss %.7g, oracle %.7g" % (dt, (l1 + l2).item(), float(np.mean(totals))))
+        n = TC.check_gradients(got, ref, "CMFlow-T ragged clip vs oracle %s mean" % dt, bounds, whole, loose=loose)
+        assert n >= 184
+        if dt == torch.float32:                                      # the loss as in check 4: against the fp32 oracle, 1e-4 * max(1, |ref|)
+            assert abs((l1 + l2).item() - float(np.mean(totals))) < 1e-4 * max(1.0, abs(float(np.mean(totals))))
+
+
+def test_cmflow_t_step_ragged_clip_carries_gfeat_and_ignores_the_padding(dev):
+    """7 / 5 for CMFlow-T through TrainStep: the recurrent branch of forward_loss_ragged hands the first frame's gfeat to the second
+    frame DETACHED (clip_util.py:54).  The second frame's gradient bucket -- it passes the GRU and the broadcast of its output over all
+    Nmax rows -- is bit-identical for zeros and +-1e4 in the padded slots of inputs and labels of both frames.  Then a two-frame clip
+    through step_ragged: both steps run, gfeat is replaced per frame, the GRU's weights move, no BN buffer moves."""
+    from cmflow_amd.train import TrainStep
+    counts = RC.COUNTS5
+    net = _net(dev, t=True)
+    step = TrainStep(net, vr_thres=0.3)
+    assert step.recurrent
+    frames = {fill: (TC.padded(RC.make_case(counts, RC.SEED5)[0], counts, 300, 256, fill),
+                     TC.padded(RC.make_case(counts, TC.SEED_T2)[0], counts, 300, 256, fill, fill_seed=2)) for fill in ("big", "zeros")}
+    res = {}
+    for fill, (f1, f2) in frames.items():
+        step.reset_clip()
+        l1 = step.forward_loss_ragged(_to(f1, dev), validate=True)[0]
+        g1 = step.gfeat
+        assert g1.shape == (len(counts), 256) and g1.requires_grad
+        l2, _, _, flat = _ragged_gradient(step, f2, dev)
+        assert step.gfeat is not g1 and not torch.equal(step.gfeat.detach(), g1.detach())
+        assert net.gru.weight_ih_l0.grad.any() and net.gru.weight_hh_l0.grad.any() and torch.isfinite(flat).all()
+        res[fill] = (l1.detach(), l2, g1.detach().clone(), flat)
+    print("CMFlow-T second frame, zeros vs +-1e4 padding: differing bucket elements %d of %d"
+          % (int((res["big"][3] != res["zeros"][3]).sum()), res["big"][3].numel()))
+    for x, y in zip(res["big"], res["zeros"]):
+        assert torch.equal(x, y)
+    # the clip through the optimizer step
+    before ={k: v.clone() for k, v in net.state_dict().items() if "running_" in k or "num_batches" in k}
+    w0 = net.gru.weight_hh_l0.detach().clone()
+    step.reset_clip()
+    f1, f2 = (_to(f, dev) for f in frames["big"])
+    s1 = step.step_ragged(f1, validate=True)[0]
+    g1 = step.gfeat
+    s2 = step.step_ragged(f2, validate=True)[0]
+    assert torch.isfinite(s1) and torch.isfinite(s2) and torch.equal(s1, res["big"][0])
+    assert step.gfeat is not g1 and torch.isfinite(step.gfeat).all()
+    assert not torch.equal(net.gru.weight_hh_l0.detach(), w0)
+    sd = net.state_dict()
+    assert all(torch.equal(sd[k], v) for k, v in before.items())
+
+
+def test_refusals(dev):
+    """8. Train-mode BatchNorm, RaFlow, bad counts; forward_ragged itself still refuses autograd."""
+    from cmflow_amd.raflow import RaFlow
+    from cmflow_amd.train import TrainStep
+    counts, seed = TC.CASES["counts5"]
+    net = _net(dev)
+    pb = _to(TC.padded(RC.make_case(counts, seed)[0], counts, 300, 256), dev)
+    args = (pb["pc1"], pb["pc2"], pb["ft1"], pb["ft2"])
+    net.train()
+    with pytest.raises(RuntimeError, match="eval"):
+        net.forward_ragged_train(*args, pb["n1"], pb["n2"], None)
+    step = TrainStep(net, vr_thres=0.3)
+    with pytest.raises(RuntimeError, match="eval"):
+        step.step_ragged(pb)
+    net.eval()
+    with pytest.raises(RuntimeError, match="no_grad"):
+        net.forward_ragged(*args, pb["n1"], pb["n2"])
+    for k, col, v in (("n2", 4, 7), ("n1", 0, 301), ("n1", 2, 0)):
+        bad = {"n1": pb["n1"].clone(), "n2": pb["n2"].clone()}
+        bad[k][col] = v
+        with pytest.raises(ValueError):
+            net.forward_ragged_train(*args, bad["n1"], bad["n2"], None, validate=True)
+    with pytest.raises(ValueError, match="label_m"):
+        net.forward_ragged_train(*args, pb["n1"], pb["n2"], torch.zeros(len(counts), 299, device=dev))
+
+    class A:
+        num_points, stat_thres, rigid_thres = 256, 0.5, 0.15
+    ra = RaFlow(A()).to(dev).eval()
+    with pytest.raises(NotImplementedError):
+        ra.forward_ragged_train(*args, pb["n1"], pb["n2"], None)
+    with pytest.raises(NotImplementedError):
+        TrainStep(ra).step_ragged(pb)
