@@ -64,6 +64,7 @@ SIGNATURES = {
     "cmf_setconv_sizes": [_vp, _vp, _vp, _vp, _vp],
     "cmf_setconv_forward": [_vp, _vp],
     "cmf_setconv_backward": [_vp, _vp],
+    "cmf_setconv_path": [_vp],
     "cmf_setconv_bn_offsets": [_vp, _vp],
     "cmf_mlp_sizes": [_vp, _vp, _vp, _vp],
     "cmf_mlp_forward": [_vp, _vp],

@@ -45,12 +45,18 @@ inline bool bnb_gather_on() { static const bool on = cmf_env_on("CMF_BNB_GATHER"
 // per launch the passes' fixed costs (constants and weights into LDS per workgroup, a statistics row per wave, the re-gather per
 // pass) ate what the 3x lower HBM traffic saved.]  Inference (one pass, cmf_setconv_chain_infer) is where the chain pays most:
 // forward 5.91 -> 5.56 ms.
-inline bool chain_train(const cmf_setconv_desc *d)
+// Which way a block's neighbour-slot layers go -- 0: the per-layer kernels, 1: the chain's inference pass (no backward call to follow),
+// 2: the chain's training passes (a backward call follows; its statistics rows want whole 128-row tiles).  The ONE predicate behind
+// the dispatch of cmf_setconv_forward / _backward, the batched inference launch and cmf_setconv_path.
+inline int setconv_path(const cmf_setconv_desc *d)
 {
     const long long M = (long long)d->B * d->N * d->S;
-    return !d->training && !d->inference && cmf_setconv_chain_supported(d->N, d->S, d->O1, d->C[0], d->C[1], M) && M % 128 == 0 &&
-           d->ldy % 4 == 0 && ((uintptr_t)d->y & 15) == 0;
+    if (d->training || !cmf_setconv_chain_supported(d->N, d->S, d->O1, d->C[0], d->C[1], M) || d->ldy % 4 != 0 || ((uintptr_t)d->y & 15) != 0)
+        return 0;
+    if (d->inference) return 1;
+    return M % 128 == 0 ? 2 : 0;
 }
+inline bool chain_train(const cmf_setconv_desc *d) { return setconv_path(d) == 2; }
 
 struct Bump {
     float *base;
@@ -521,7 +527,7 @@ static int setconv_forward_part(const cmf_setconv_desc *d, void *st, int part)
     if (!d->training) CMF_TRY(fold_all_eval(d, L, st));
     if (!d->idx_ready) CMF_TRY(cmf_ball_query_defined(d->B, d->N, d->N, d->radius, d->S, d->xyz, d->xyz, L.idx, st));
     // Three ways to the pooled rows L.x; the per-point tail behind them is the same sequence for all (eval mode: its folds are no-ops).
-    if (!d->training && d->inference && cmf_setconv_chain_supported(d->N, d->S, O1, C2, C3, M) && d->ldy % 4 == 0 && ((uintptr_t)d->y & 15) == 0) {
+    if (setconv_path(d) == 1) {
         // inference of the narrow block (first encoder): layers 1-3 and the max over the ball as ONE register-chain kernel
         // (csrc/setconv_chain.hip; every layer bit-identical to the per-layer kernels) -- nothing but the pooled rows is written
         CMF_TRY(cmf_setconv_chain_infer(M, d->N, d->S, L.idx, d->xyz, d->y, d->ldy, d->wx, d->ldwx, L.bn[0].block(), L.bn[1].block(),
@@ -565,6 +571,10 @@ static int setconv_forward_part(const cmf_setconv_desc *d, void *st, int part)
 }
 
 extern "C" int cmf_setconv_forward(const cmf_setconv_desc *d, void *st) { return setconv_forward_part(d, st, 0); }
+
+// the way cmf_setconv_forward / _backward take for this descriptor (setconv_path above; shape fields, d->training, d->inference, d->ldy
+// and the alignment of d->y are read, nothing is launched)
+extern "C" int cmf_setconv_path(const cmf_setconv_desc *d) { return d ? setconv_path(d) : 0; }
 
 // counts: NULL (dense), or per block the device array (B) int32 of its samples' point counts (ragged samples: cmf_setconv_queries_counted)
 static int setconv_queries(int n, const cmf_setconv_desc *descs, const int *const *counts, void *stream)
@@ -904,8 +914,7 @@ static bool infer_batchable(int n, const cmf_setconv_desc *descs)
     for (int i = 0; i < n; ++i) {
         const cmf_setconv_desc &d = descs[i];
         const long long M = (long long)d.B * d.N * d.S;
-        if (d.training || !d.inference || !d.idx_ready || !cmf_setconv_chain_supported(d.N, d.S, d.O1, d.C[0], d.C[1], M) || d.ldy % 4 ||
-            ((uintptr_t)d.y & 15) || M >= (1ll << 31)) return false;
+        if (setconv_path(&d) != 1 || !d.idx_ready || M >= (1ll << 31)) return false;
         for (int l = 0; l < 6; ++l) if (!d.rmean[l] || !d.rvar[l]) return false;
     }
     return true;

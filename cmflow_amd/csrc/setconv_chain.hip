@@ -10,7 +10,8 @@
 // register, already the B operand of the next layer's MFMA steps: step r contracts the channel pair {c(r, 0), c(r, 1)} when lane
 // (j, h) supplies its register r, and the weights are pre-loaded in the matching order, A_r[lane (i, h)] = W[i][c(r, h)].
 // That pair order -- {0,4} {1,5} {2,6} {3,7} {8,12} ... -- is exactly the order in which thin_fwd / cmf_gemm consume k (a lane's
-// 16-byte fragment feeds four steps), so every layer output is bit-identical to the per-layer kernels' (tests/test_gpu_gemm.py).
+// 16-byte fragment feeds four steps), so every layer output is bit-identical to the per-layer kernels': tests/test_gpu_setconv_chain.py
+// asserts it for the pooled output of every mode and shape class below, and compares outputs and all gradients with an fp64 reference.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>

@@ -1291,6 +1291,10 @@ def multi_scale_set_conv(encoder, modules, streams, xyz_t, y_all, counts=None):
 def set_conv(module, xyz_t, y):
     """module: PointLocalFeature; y: (B,N,O1) view of the hoisted first-conv features."""
     params, bns = set_conv_params(module)
+    if not torch.is_grad_enabled():
+        # no backward call can follow: the Function must see inputs that need no gradient (needs_input_grad reports the tensors'
+        # requires_grad even under no_grad), or the block call keeps everything a backward pass reads and never takes its inference forms
+        params, y = [p.detach() for p in params], y.detach()
     fn = SetConvBlockFn if USE_BLOCK_CALLS else SetConvFn
     return fn.apply(xyz_t, y, module.radius, module.nsample, bns, bns[0].training, *params)
 

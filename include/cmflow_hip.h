@@ -463,6 +463,12 @@ long long cmf_mem_stats(void);
 int cmf_setconv_queries(int n, const cmf_setconv_desc *descs, void *stream);
 int cmf_setconv_forward(const cmf_setconv_desc *d, void *stream);
 int cmf_setconv_backward(const cmf_setconv_desc *d, void *stream);
+/* Which kernels cmf_setconv_forward / _backward run the neighbour-slot layers of this descriptor with -- 0: the per-layer kernels,
+ * 1: the register chain's inference pass (csrc/setconv_chain.hip; eval-mode BatchNorm, d->inference), 2: the chain's training passes
+ * (eval-mode BatchNorm with a backward call to follow, M = B*N*S a multiple of 128).  Host arithmetic with the predicate the dispatch
+ * itself uses: B, N, S, O1, C, training, inference, ldy and the alignment of d->y are read; nothing is launched.  For tests and
+ * tools that must know a call exercised the kernel they mean. */
+int cmf_setconv_path(const cmf_setconv_desc *d);
 /* The optimizer step of the reference's loop (main.py:107: torch.optim.Adam with L2 weight decay) over a flat gradient bucket in ONE
  * launch: grad / m / v are flat arrays of `total` floats in bucket order, params[t] the address of tensor t and offsets[t] its first
  * element in the bucket (offsets[n_tensors] = total; both tables in device memory).  step >= 1 is the count INCLUDING this update.

@@ -28,6 +28,9 @@ def test_export_table_is_complete():
                  "gather_points_grad_wrapper", "furthest_point_sampling_wrapper", "knn_wrapper", "three_nn_wrapper",
                  "three_interpolate_wrapper", "three_interpolate_grad_wrapper"):
         assert callable(getattr(ext, name))
+    from cmflow_amd import _lib
+    for name in ("cmf_setconv_path",):                      # C-ABI queries the tests themselves rely on
+        assert name in _lib.SIGNATURES and callable(getattr(_lib.lib(), name))
 
 
 @pytest.mark.parametrize("B,N,m", [(3, 256, 64), (2, 1000, 128), (1, 37, 37)])
