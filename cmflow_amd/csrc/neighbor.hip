@@ -1069,15 +1069,124 @@ extern "C" int cmf_knn_counted(int b, int n, int s, int nsample, const float *xy
 
 // ---- rest of the pointnet2_cuda neighbour surface (not called by CMFlow) -------------------
 
-// knn_wrapper (lib/src/interpolate_gpu.cu:9-57): unknown (b,n,3) queries, known (b,m,3) -> dist2, idx (b,n,k).
+// kNN for 64 < k <= 200 (the upper part of knn_wrapper's range).  knn_kernel keeps a lane's whole list in that lane's registers,
+// which ends at K = 64 (128 live registers); here a WAVE owns a query and the sorted list is spread over it: slot t sits in lane
+// t % 64, register row t / 64, R = ceil(k / 64) rows (2 .. 4).  The wave takes 64 points of the LDS tile per step, one per lane
+// (consecutive float4s: conflict free), with the PLAIN = true arithmetic of knn_kernel statement for statement.  The k-th best
+// distance is wave-uniform, so one ballot of `d < kth` names the candidates that enter; they are inserted one at a time in
+// ascending lane order = ascending point index (the first-seen rule), and after each insertion the ballot is taken again against
+// the new k-th distance.  An insertion is: position = number of list entries <= d (a compare + population count per row: the
+// list is sorted, so these are a prefix -- the slot knn_kernel's strict '<' bubble-up stops at), then every slot from there on
+// takes its lower neighbour's pair: one wave-wide DPP shift per row, whose lane 0 is fed lane 63 of the row below.  Rows hold
+// 64 R >= k slots; what is pushed past slot k - 1 stays sorted behind it and is never read.  Slots that never received a point
+// (m < k) are written as index 0 / distance 0 like knn_kernel's.
+constexpr int KNNW_WAVES = 4;       // queries per workgroup (they share the tile)
+
+__device__ __forceinline__ int knnw_shift_in(int carry, int v)       // lane l <- v of lane l - 1; lane 0 <- carry
+{
+    return __builtin_amdgcn_update_dpp(carry, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+}
+
+template <int R>
+__global__ __launch_bounds__(KNNW_WAVES *CMF_WAVE) void knn_wave_kernel(
+    int m, int n, int k, const float *__restrict__ known, const float *__restrict__ unknown,
+    int *__restrict__ idx, float *__restrict__ dist2)
+{
+    __shared__ float4 tile[KNN_TILE];
+    const int bs = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int q = blockIdx.x * KNNW_WAVES + (tid >> 6);
+    const bool live = q < n;                                    // wave-uniform
+    const float *pts = known + (size_t)bs * m * 3;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    if (live) {
+        const float *c = unknown + ((size_t)bs * n + q) * 3;
+        qx = c[0]; qy = c[1]; qz = c[2];
+    }
+    float bd[R];
+    int bi[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { bd[r] = __builtin_inff(); bi[r] = 0; }
+    const int kl = (k - 1) & 63;                                // slot k - 1 is lane kl of row R - 1 (64 (R - 1) < k <= 64 R)
+    float kth = __builtin_inff();
+
+    for (int base = 0; base < m; base += KNN_TILE) {
+        const int len = min(KNN_TILE, m - base);
+        __syncthreads();
+        for (int i = tid; i < len; i += KNNW_WAVES * CMF_WAVE) {
+            const float x = pts[(size_t)(base + i) * 3 + 0];
+            const float y = pts[(size_t)(base + i) * 3 + 1];
+            const float z = pts[(size_t)(base + i) * 3 + 2];
+            tile[i] = make_float4(x, y, z, 0.f);
+        }
+        __syncthreads();
+        if (!live) continue;                                    // a wave without a query only stages and meets the barriers
+        for (int j0 = 0; j0 < len; j0 += CMF_WAVE) {
+            const bool have = j0 + lane < len;
+            const float4 p = tile[have ? j0 + lane : 0];
+            const float dx = qx - p.x;
+            const float dy = qy - p.y;
+            const float dz = qz - p.z;
+            const float xx = dx * dx;
+            const float yy = dy * dy;
+            const float zz = dz * dz;
+            const float sxy = xx + yy;
+            const float v = sxy + zz;
+            unsigned long long cand = __ballot(have && v < kth);
+            while (cand) {
+                const int c = __builtin_ctzll(cand);            // lowest lane = lowest point index
+                cand &= cand - 1;
+                const int dvb = __builtin_amdgcn_readlane(__float_as_int(v), c);
+                const float dv = __int_as_float(dvb);
+                const int iv = base + j0 + c;
+                int pos = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) pos += __popcll(__ballot(bd[r] <= dv));
+                int cd = 0, ci = 0;                             // row 0, lane 0 is slot 0: never behind pos
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int od = __float_as_int(bd[r]), oi = bi[r];
+                    const int pd = knnw_shift_in(cd, od), pi = knnw_shift_in(ci, oi);
+                    cd = __builtin_amdgcn_readlane(od, 63); ci = __builtin_amdgcn_readlane(oi, 63);
+                    const int t = r * CMF_WAVE + lane;
+                    bd[r] = __int_as_float(t > pos ? pd : (t == pos ? dvb : od));
+                    bi[r] = t > pos ? pi : (t == pos ? iv : oi);
+                }
+                kth = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bd[R - 1]), kl));
+                cand &= __ballot(v < kth);
+            }
+        }
+    }
+    if (live) {
+        int *o = idx + ((size_t)bs * n + q) * k;
+        float *d = dist2 + ((size_t)bs * n + q) * k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int t = r * CMF_WAVE + lane;
+            if (t < k) {
+                o[t] = (bd[r] == __builtin_inff()) ? 0 : bi[r];
+                d[t] = (bd[r] == __builtin_inff()) ? 0.0f : bd[r];
+            }
+        }
+    }
+}
+
+// knn_wrapper (lib/src/interpolate_gpu.cu:9-57): unknown (b,n,3) queries, known (b,m,3) -> dist2, idx (b,n,k), k <= 200.
 extern "C" int cmf_knn_points(int b, int n, int m, int k, const float *unknown, const float *known,
                               float *dist2, int *idx, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && n >= 0 && m >= 0 && k > 0 && k <= 64);      // the reference allows k <= 200
+    CMF_CHECK_ARG(b >= 0 && n >= 0 && m >= 0 && k > 0 && k <= 200);     // the reference's range
     if (b == 0 || n == 0) return 0;
-    CMF_CHECK_ARG(unknown && known && dist2 && idx);
-    dim3 grid(cmf_divup(n, CMF_WAVE), b), block(CMF_WAVE);
+    CMF_CHECK_ARG(unknown && (known || m == 0) && dist2 && idx);        // an empty cloud has no storage: every slot reads 0
     hipStream_t st = (hipStream_t)stream;
+    if (k > 64) {                                                       // the list no longer fits a lane: one wave per query
+        const dim3 wgrid(cmf_divup(n, KNNW_WAVES), b), wblock(KNNW_WAVES * CMF_WAVE);
+        if (k <= 128)      hipLaunchKernelGGL(knn_wave_kernel<2>, wgrid, wblock, 0, st, m, n, k, known, unknown, idx, dist2);
+        else if (k <= 192) hipLaunchKernelGGL(knn_wave_kernel<3>, wgrid, wblock, 0, st, m, n, k, known, unknown, idx, dist2);
+        else               hipLaunchKernelGGL(knn_wave_kernel<4>, wgrid, wblock, 0, st, m, n, k, known, unknown, idx, dist2);
+        return cmf_launch_status();
+    }
+    dim3 grid(cmf_divup(n, CMF_WAVE), b), block(CMF_WAVE);
     if (k <= 4)       hipLaunchKernelGGL((knn_kernel<4, true>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
     else if (k <= 8)  hipLaunchKernelGGL((knn_kernel<8, true>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
     else if (k <= 16) hipLaunchKernelGGL((knn_kernel<16, true>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2);

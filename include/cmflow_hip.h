@@ -398,7 +398,9 @@ int cmf_gather_points_grad(int b, int c, int n, int npoints, const float *grad_o
 /* furthest_point_sampling_kernel_launcher (sampling_gpu.cu:212-250): temp (b,n) pre-filled with 1e10 */
 int cmf_furthest_point_sampling(int b, int n, int m, const float *dataset, float *temp, int *idxs, void *stream);
 /* knn_kernel_launcher_fast (interpolate_gpu.cu:60-78): k nearest `known` points per `unknown`, ascending,
- * first-seen wins ties, squared distances; k <= 64 here (reference: k <= 200) */
+ * first-seen wins ties, squared distances; 0 < k <= 200, the reference's range (k <= 64: a lane per query with its list in
+ * registers; above: a wave per query, the list spread over its lanes).  Slots behind a cloud of m < k points read index 0,
+ * distance 0. */
 int cmf_knn_points(int b, int n, int m, int k, const float *unknown, const float *known,
                    float *dist2, int *idx, void *stream);
 /* three_nn_kernel_launcher_fast (interpolate_gpu.cu:127-146) */
