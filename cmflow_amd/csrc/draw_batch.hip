@@ -1,0 +1,162 @@
+// cmf_draw_batch: one training batch drawn from a split that lives on the device (cmflow_amd/dataset.py DeviceSplit) -- frame
+// choice, the reference's per-frame resampling to `npoints` (dataset/vod.py:95-121 sample_points = dataset._resample) and the model's
+// layout (main_util.py:21-36 extract_data_info) in ONE launch.  One workgroup per (slot, cloud).
+//
+// Sampling contract (include/cmflow_hip.h, DESIGN.md "Device-resident split"): Philox4x32-10, keyed per call from (seed, draw),
+// counter (slot, cloud, i, 0), word 0 of the output.
+//   n <  N: points 0 .. n-1 in order, then N - n independent draws mulhi(u32, n)                          -- no sort;
+//   n >= N: point i carries the 64-bit key (u32 << 32) | i; the keys go to LDS, padded with maximal keys to the next power of two,
+//           a bitonic sort puts them in ascending order and the low words of the first N are the draw (a uniformly random
+//           N-subset in uniformly random order; keys are distinct by construction).
+// The chosen indices stay in LDS; the gather then runs output tensor by output tensor with consecutive lanes on consecutive
+// addresses of the output (the reads are 4-byte picks from 56- / 24-byte rows of a table that sits in L2).
+#include "cmf_common.h"
+#include "../../include/cmflow_hip.h"
+
+namespace {
+
+constexpr int DRAW_COLS1 = 14, DRAW_COLS2 = 6;
+constexpr int DRAW_THREADS_SMALL = 256, DRAW_THREADS_LARGE = 1024;     // the large form from 4096 sort slots on
+
+struct Philox { uint32_t x, y, z, w; };
+
+__host__ __device__ inline uint32_t draw_mulhi(uint32_t a, uint32_t b)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __umulhi(a, b);
+#else
+    return (uint32_t)(((unsigned long long)a * b) >> 32);
+#endif
+}
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): ten rounds of two 32 x 32 -> 64 multiplies, key bumped by the Weyl constants
+__host__ __device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = draw_mulhi(M0, c0), l0 = M0 * c0, h1 = draw_mulhi(M1, c2), l1 = M1 * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += W0;
+        k1 += W1;
+    }
+    return Philox{c0, c1, c2, c3};
+}
+
+struct DrawArgs {
+    int B, N, F, max_points;
+    const float *tab1, *tab2;
+    const int *off1, *off2;
+    const float *trans, *interval;
+    const int *frames;
+    uint32_t k0, k1;
+    float *pc1, *pc2, *ft1, *ft2, *gt_trans, *flow_label, *fg_mask, *interval_out, *radar_u, *radar_v, *opt_flow;
+    int *idx1, *idx2;
+};
+
+__global__ __launch_bounds__(DRAW_THREADS_LARGE) void draw_batch_kernel(const DrawArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long draw_keys[];     // [P] sort keys, or [N] ints when n < N
+    int *sel = reinterpret_cast<int *>(draw_keys);
+    const int slot = blockIdx.x, cloud = blockIdx.y, t = threadIdx.x, nt = blockDim.x;
+    const int N = a.N;
+    const int f = min(max(a.frames[slot], 0), a.F - 1);                    // a bad id gives wrong data, not a wild access
+    const int *off = cloud ? a.off2 : a.off1;
+    const long long start = off[f];
+    const int n = min(max(off[f + 1] - off[f], 1), a.max_points);          // the LDS was sized for max_points
+    int sh;                                                                // the draw of output j is sel[j << sh]
+    if (n < N) {
+        sh = 0;
+        for (int j = t; j < N; j += nt)
+            sel[j] = j < n ? j : (int)draw_mulhi(philox4x32_10(slot, cloud, j - n, 0u, a.k0, a.k1).x, (uint32_t)n);
+        __syncthreads();
+    } else {
+        sh = 1;                                                            // low word of key j (little endian)
+        int P = 1;
+        while (P < n) P <<= 1;
+        for (int i = t; i < P; i += nt)
+            draw_keys[i] = i < n ? ((unsigned long long)philox4x32_10(slot, cloud, i, 0u, a.k0, a.k1).x << 32) | (unsigned)i : ~0ull;
+        __syncthreads();
+        for (int k = 2; k <= P; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int h = t; h < (P >> 1); h += nt) {
+                    const int lo = ((h & ~(j - 1)) << 1) | (h & (j - 1)), hi = lo | j;
+                    const unsigned long long x = draw_keys[lo], y = draw_keys[hi];
+                    if ((x > y) == ((lo & k) == 0)) {
+                        draw_keys[lo] = y;
+                        draw_keys[hi] = x;
+                    }
+                }
+                __syncthreads();
+            }
+    }
+    const size_t sN = (size_t)slot * N;
+    if (cloud == 0) {
+        const float *tab = a.tab1 + (size_t)start * DRAW_COLS1;
+        for (int e = t; e < 3 * N; e += nt) {                              // (B,3,N): coordinates and features
+            const int c = e / N, j = e - c * N;
+            const float *row = tab + (size_t)sel[j << sh] * DRAW_COLS1;
+            a.pc1[3 * sN + e] = row[c];
+            a.ft1[3 * sN + e] = row[3 + c];
+        }
+        for (int e = t; e < 3 * N; e += nt) {                              // (B,N,3): labels
+            const int j = e / 3, c = e - 3 * j;
+            a.flow_label[3 * sN + e] = tab[(size_t)sel[j << sh] * DRAW_COLS1 + 6 + c];
+        }
+        for (int e = t; e < 2 * N; e += nt)                                // (B,N,2): optical flow
+            a.opt_flow[2 * sN + e] = tab[(size_t)sel[(e >> 1) << sh] * DRAW_COLS1 + 12 + (e & 1)];
+        for (int j = t; j < N; j += nt) {                                  // (B,N)
+            const int i = sel[j << sh];
+            const float *row = tab + (size_t)i * DRAW_COLS1;
+            a.fg_mask[sN + j] = row[9];
+            a.radar_u[sN + j] = row[10];
+            a.radar_v[sN + j] = row[11];
+            a.idx1[sN + j] = i;
+        }
+        for (int e = t; e < 16; e += nt) a.gt_trans[(size_t)slot * 16 + e] = a.trans[(size_t)f * 16 + e];
+        if (t == 0) a.interval_out[slot] = a.interval[f];
+    } else {
+        const float *tab = a.tab2 + (size_t)start * DRAW_COLS2;
+        for (int e = t; e < 3 * N; e += nt) {
+            const int c = e / N, j = e - c * N;
+            const float *row = tab + (size_t)sel[j << sh] * DRAW_COLS2;
+            a.pc2[3 * sN + e] = row[c];
+            a.ft2[3 * sN + e] = row[3 + c];
+        }
+        for (int j = t; j < N; j += nt) a.idx2[sN + j] = sel[j << sh];
+    }
+}
+
+}  // namespace
+
+extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2, const int *off1,
+                              const int *off2, const float *trans, const float *interval, const int *frames,
+                              unsigned long long seed, unsigned long long draw,
+                              float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                              float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream)
+{
+    CMF_CHECK_ARG(B >= 1 && npoints >= 1 && npoints <= CMF_DRAW_MAX_NPOINTS && nframes >= 1);
+    CMF_CHECK_ARG(max_points >= 1 && max_points <= CMF_DRAW_MAX_POINTS);
+    CMF_CHECK_ARG(tab1 && tab2 && off1 && off2 && trans && interval && frames);
+    CMF_CHECK_ARG(pc1 && pc2 && ft1 && ft2 && gt_trans && flow_label && fg_mask && interval_out && radar_u && radar_v && opt_flow && idx1 && idx2);
+    int P = 1;
+    while (P < max_points) P <<= 1;
+    const size_t lds = std::max((size_t)P * 8, (size_t)npoints * 4);       // <= 128 KiB by the two limits above
+    static CmfPerDevice attr_set;
+    int attr_dev;
+    if (attr_set.need(attr_dev)) {
+        const hipError_t e = hipFuncSetAttribute((const void *)draw_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 CMF_DRAW_MAX_POINTS * 8);
+        if (e != hipSuccess) return (int)e;
+        attr_set.done(attr_dev);
+    }
+    const Philox key = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), 0u, 0u);
+    DrawArgs a{B, npoints, nframes, max_points, tab1, tab2, off1, off2, trans, interval, frames, key.x, key.y,
+               pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, idx1, idx2};
+    const int threads = P >= 4096 ? DRAW_THREADS_LARGE : DRAW_THREADS_SMALL;
+    hipLaunchKernelGGL(draw_batch_kernel, dim3(B, 2), dim3(threads), lds, (hipStream_t)stream, a);
+    return cmf_launch_status();
+}

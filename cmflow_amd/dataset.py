@@ -2,7 +2,8 @@
 (vodDataset :14-137; format described in src/GETTING_STARTED.md:97-106), of ``dataset/vod_clip.py`` (vodClipDataset
 :14-198, the mini-clip loader CMFlow-T trains on) and of ``extract_data_info`` / ``extract_data_info_clip``
 (main_util.py:21-36, clip_util.py:81-96); ``collate_ragged`` / ``extract_data_info_ragged`` batch the evaluation-mode items (whole
-frames of their own sizes) for ``CMFlow.forward_ragged``.
+frames of their own sizes) for ``CMFlow.forward_ragged``; ``DeviceSplit`` keeps a whole training split on the device and draws
+each step's batch there (``cmf_draw_batch``).
 
 One sample = one JSON file ``<root>/<partition>/<clip>/<k>_*.json`` with
     pc1, pc2          [n][5]  x, y, z, RCS, v_r          (features fed to the net: [v_r, RCS, RCS], vod.py:62-63)
@@ -225,6 +226,127 @@ def as_batch_dict_ragged(info):
     d = as_batch_dict(info[:11])
     d["n1"], d["n2"] = info[11], info[12]
     return d
+
+
+DRAW_MAX_POINTS = 16384          # CMF_DRAW_MAX_POINTS of include/cmflow_hip.h: the per-frame cap of cmf_draw_batch (sort keys in LDS)
+_MASK64 = (1 << 64) - 1
+
+
+class DeviceSplit:
+    """A training split decoded once and kept on the device as whole frames; every step's batch is then produced there by one
+    kernel (``cmf_draw_batch``: frame choice, the reference's per-frame resampling to ``npoints``, the layout of
+    extract_data_info) -- no workers, no per-step host work, no per-step host-to-device copy.
+
+    Packed CSR-style over F frames: ``tab1`` (sum n1, 14) float32 per point of cloud 1 = xyz 3 | features 3 | label 3 | mask |
+    radar_u | radar_v | opt_flow 2; ``tab2`` (sum n2, 6) = xyz 3 | features 3; ``off1``, ``off2`` (F+1) int32; ``trans`` (F,16);
+    ``interval`` (F); ``clips``: [first, last) frame range of every clip (from_dataset on a vodClipDataset), else None.
+    Packing is host code and works on any device; drawing needs the GPU (no CPU fallback)."""
+
+    KEYS = ("pc1", "pc2", "ft1", "ft2", "gt_trans", "flow_label", "fg_mask", "interval", "radar_u", "radar_v", "opt_flow")
+
+    def __init__(self, tab1, tab2, off1, off2, trans, interval, max_points, clips=None):
+        self.tab1, self.tab2, self.off1, self.off2, self.trans, self.interval = tab1, tab2, off1, off2, trans, interval
+        self.max_points = int(max_points)
+        self.clips = clips
+        self.device = tab1.device
+
+    def __len__(self):
+        return self.off1.numel() - 1
+
+    def to(self, device):
+        """The same split on another device (pack once on the host, keep a copy per GPU)."""
+        return DeviceSplit(*(t.to(device) for t in (self.tab1, self.tab2, self.off1, self.off2, self.trans, self.interval)),
+                           self.max_points, self.clips)
+
+    @classmethod
+    def from_items(cls, items, device, clips=None):
+        """items: whole-frame 11-tuples exactly as ``_sample_item`` returns them when ``ds.eval`` is true (a training partition
+        opened with ``args.eval = True`` gives pseudo labels and optical-flow columns, not resampled)."""
+        items = list(items)
+        if len(items) == 0:
+            raise ValueError("DeviceSplit: no frames")
+        t1, t2, tr, iv = [], [], [], []
+        for k, it in enumerate(items):
+            pos1, pos2, f1, f2, trans, labels, mask, interval, ru, rv, opt = (np.asarray(v, dtype=np.float32) for v in it)
+            n1, n2 = pos1.shape[0], pos2.shape[0]
+            if n1 < 1 or n2 < 1:
+                raise ValueError("DeviceSplit: frame %d has no points" % k)
+            if max(n1, n2) > DRAW_MAX_POINTS:
+                raise ValueError("DeviceSplit: frame %d has %d points, more than the %d cmf_draw_batch sorts in one workgroup's LDS"
+                                 % (k, max(n1, n2), DRAW_MAX_POINTS))
+            t1.append(np.concatenate([pos1, f1, labels, mask[:, None], ru[:, None], rv[:, None], opt], axis=1))
+            t2.append(np.concatenate([pos2, f2], axis=1))
+            tr.append(trans.reshape(16))
+            iv.append(interval)
+        c1, c2 = np.cumsum([0] + [t.shape[0] for t in t1]), np.cumsum([0] + [t.shape[0] for t in t2])
+        if max(c1[-1], c2[-1]) >= 2 ** 31:
+            raise ValueError("DeviceSplit: more than 2^31 - 1 points")
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)
+        return cls(to(np.concatenate(t1), np.float32), to(np.concatenate(t2), np.float32), to(c1, np.int32), to(c2, np.int32),
+                   to(np.stack(tr), np.float32), to(np.array(iv), np.float32),
+                   max(int(np.diff(c1).max()), int(np.diff(c2).max())), clips)
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        """One pass over a vodDataset / vodClipDataset opened with ``args.eval = True`` (whole frames); the clip dataset's
+        ``clips_info`` gives each clip's frame range."""
+        if not ds.eval:
+            raise ValueError("DeviceSplit.from_dataset: open the dataset with args.eval = True (whole frames, not resampled)")
+        clips = [tuple(c["index"]) for c in ds.clips_info] if isinstance(ds, vodClipDataset) else None
+        return cls.from_items((ds[i] for i in range(len(ds))), device, clips)
+
+    def draw(self, frames, npoints, seed, draw):
+        """One batch: slot s holds frame ``frames[s]`` resampled to ``npoints`` as ``dataset._resample`` does (n < npoints: all n
+        points in order, then uniform duplicates; n >= npoints: a uniformly random subset in uniformly random order), generator
+        Philox4x32-10 keyed by (seed, draw) -- a slot's result depends on (seed, draw, slot, frame) only.
+        -> the dict of as_batch_dict plus ``idx1``, ``idx2`` (B, npoints) int32, the drawn point of every position."""
+        from . import _lib
+        if not self.tab1.is_cuda:
+            raise RuntimeError("DeviceSplit.draw: the split is on %s; batches are drawn on the GPU only (no CPU fallback)" % self.device)
+        frames = torch.as_tensor(frames, dtype=torch.int32, device=self.device).contiguous()
+        B, N = int(frames.numel()), int(npoints)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        out = dict(zip(self.KEYS, (f32(B, 3, N), f32(B, 3, N), f32(B, 3, N), f32(B, 3, N), f32(B, 4, 4), f32(B, N, 3), f32(B, N), f32(B),
+                                   f32(B, N), f32(B, N), f32(B, N, 2))))
+        out["idx1"] = torch.empty((B, N), dtype=torch.int32, device=self.device)
+        out["idx2"] = torch.empty((B, N), dtype=torch.int32, device=self.device)
+        fp, ip = (lambda t: _lib.dev_ptr(t, torch.float32)), (lambda t: _lib.dev_ptr(t, torch.int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().cmf_draw_batch(
+                B, N, len(self), self.max_points, fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans),
+                fp(self.interval), ip(frames), int(seed) & _MASK64, int(draw) & _MASK64, *(fp(out[k]) for k in self.KEYS),
+                ip(out["idx1"]), ip(out["idx2"]), _lib.stream_ptr()), "cmf_draw_batch")
+        return out
+
+    def _order(self, count, seed, epoch):
+        g = torch.Generator(device=self.device)
+        g.manual_seed((int(seed) * 0x9E3779B97F4A7C15 + int(epoch)) & _MASK64)
+        return torch.randperm(count, generator=g, device=self.device)
+
+    def epoch(self, batch_size, npoints, seed, epoch, drop_last=True):
+        """One pass over the frames in an order shuffled on the device (torch.randperm, generator seeded by (seed, epoch)): yields
+        one batch dict per step; ``draw`` = epoch * steps_per_epoch + step."""
+        F = len(self)
+        steps = F // batch_size if drop_last else -(-F // batch_size)
+        order = self._order(F, seed, epoch).to(torch.int32)
+        for step in range(steps):
+            yield self.draw(order[step * batch_size:(step + 1) * batch_size], npoints, seed, epoch * steps + step)
+
+    def epoch_clips(self, batch_size, mini_clip_len, npoints, seed, epoch):
+        """CMFlow-T: mini-clips cut as vodClipDataset cuts them (floor(len / L) per clip, remainder dropped), their order
+        shuffled; every step yields a list of L batch dicts -- frame j of every mini-clip of the batch -- which TrainStep takes
+        frame by frame between reset_clip() calls.  The last step holds the mini-clips left over (fewer than batch_size)."""
+        if self.clips is None:
+            raise ValueError("DeviceSplit.epoch_clips: no clip ranges (build the split with from_dataset on a vodClipDataset)")
+        L = int(mini_clip_len)
+        first = [a + i * L for a, b in self.clips for i in range((b - a) // L)]
+        if not first:
+            return
+        first = torch.tensor(first, dtype=torch.int32, device=self.device)[self._order(len(first), seed, epoch)]
+        steps = -(-first.numel() // batch_size)
+        for step in range(steps):
+            f0 = first[step * batch_size:(step + 1) * batch_size]
+            yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j) for j in range(L)]
 
 
 def write_sample(path, pc1, pc2, gt_labels, pse_labels, gt_mask, pse_mask, trans, opt_flow=None, radar_u=None, radar_v=None):

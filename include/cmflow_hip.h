@@ -754,6 +754,34 @@ int cmf_pseudo_labels_counted(int b, int nmax, const int *n1, const float *pc1, 
                               const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
                               float *dyn_mask, float *mseg_gt, float *residual, void *stream);
 
+/* ---- a training split that lives on the device: one batch per launch ------------------------------------------------------------
+ * cmf_draw_batch: the training batch of one step from packed whole frames (cmflow_amd/dataset.py DeviceSplit) -- frame choice, the
+ *   reference's per-frame resampling to npoints (dataset/vod.py:95-121 sample_points) and the layout of extract_data_info
+ *   (main_util.py:21-36) in one launch, one workgroup per (slot, cloud).
+ *   Packed split of nframes frames: tab1 (off1[nframes], 14) per point of cloud 1 = xyz 3 | features 3 | label 3 | mask | radar_u |
+ *   radar_v | opt_flow 2; tab2 (off2[nframes], 6) = xyz 3 | features 3; off1, off2 (nframes + 1) int32 row offsets; trans (nframes,16);
+ *   interval (nframes).  max_points: the largest point count of any frame and cloud of the split, <= CMF_DRAW_MAX_POINTS (the sort
+ *   keys of one cloud, 8 bytes a point over the next power of two, live in one workgroup's LDS: 16384 * 8 = 128 KiB of the CU's
+ *   160 KiB; the next power of two would not fit); it sizes the launch's LDS.  frames (B) int32: the frame of every slot.
+ *   -> pc1, pc2, ft1, ft2 (B,3,N); gt_trans (B,4,4); flow_label (B,N,3); fg_mask (B,N); interval_out (B); radar_u, radar_v (B,N);
+ *   opt_flow (B,N,2); idx1, idx2 (B,N) int32: the drawn point of every output position, N = npoints <= CMF_DRAW_MAX_NPOINTS.
+ *   Every float is a copy: out[..j..] = table row idx[slot][j] of the slot's frame, bit for bit.
+ *   Sampling, per (slot, cloud), for a frame of n points: u32(i) = word 0 of Philox4x32-10 with counter (slot, cloud, i, 0) and the
+ *   key of the call = words 0, 1 of Philox4x32-10 with counter (seed lo, seed hi, draw lo, draw hi) and key (0, 0).
+ *     n <  N: idx = 0 .. n-1, then for j = 0 .. N-n-1 the point (u32(j) * n) >> 32 (independent uniform draws);
+ *     n >= N: point i gets the 64-bit key (u32(i) << 32) | i; the N smallest keys in ascending order are the draw (a uniformly
+ *             random N-subset in uniformly random order; the keys are distinct).
+ *   A slot's outputs depend on (seed, draw, slot, frame) only.  tests/draw_ref.py restates the rule on the host.
+ *   Frame ids and offsets are trusted like the counts of the ragged entry points; ids are clamped to [0, nframes-1] and a frame's
+ *   count to [1, max_points] inside the kernel: a bad id gives wrong data, not an access outside the tables. */
+#define CMF_DRAW_MAX_POINTS 16384
+#define CMF_DRAW_MAX_NPOINTS 32768
+int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2, const int *off1,
+                   const int *off2, const float *trans, const float *interval, const int *frames,
+                   unsigned long long seed, unsigned long long draw,
+                   float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                   float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
