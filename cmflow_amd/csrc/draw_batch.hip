@@ -10,6 +10,8 @@
 //           N-subset in uniformly random order; keys are distinct by construction).
 // The chosen indices stay in LDS; the gather then runs output tensor by output tensor with consecutive lanes on consecutive
 // addresses of the output (the reads are 4-byte picks from 56- / 24-byte rows of a table that sits in L2).
+//
+// cmf_draw_frames (below, same tables): the frames themselves, whole and unsampled, padded to a ragged batch.
 #include "cmf_common.h"
 #include "../../include/cmflow_hip.h"
 
@@ -130,6 +132,77 @@ __global__ __launch_bounds__(DRAW_THREADS_LARGE) void draw_batch_kernel(const Dr
     }
 }
 
+// cmf_draw_frames: whole frames as a ragged batch (dataset.collate_ragged's padding rule, extract_data_info_ragged's layout).  One
+// workgroup per (chunk of FRAMES_CHUNK positions, cloud, slot); lane t holds position p0 + t and reads table row p0 + t (row 0 from
+// the frame's count on), so a wave reads 64 consecutive 56- / 24-byte rows -- whole cache lines, every byte of which one of the
+// loops below uses -- and every store runs over consecutive addresses of its output tensor.
+constexpr int FRAMES_CHUNK = 256;
+
+struct FramesArgs {
+    int B, N1, N2, F;
+    const float *tab1, *tab2;
+    const int *off1, *off2;
+    const float *trans, *interval;
+    const int *frames;
+    float *pc1, *pc2, *ft1, *ft2, *gt_trans, *flow_label, *fg_mask, *interval_out, *radar_u, *radar_v, *opt_flow;
+    int *n1, *n2;
+};
+
+__global__ __launch_bounds__(FRAMES_CHUNK) void draw_frames_kernel(const FramesArgs a)
+{
+    const int chunk = blockIdx.x, cloud = blockIdx.y, slot = blockIdx.z, t = threadIdx.x;
+    const int N = cloud ? a.N2 : a.N1;
+    const int p0 = chunk * FRAMES_CHUNK;
+    if (p0 >= N) return;                                                   // the grid covers the larger of the two clouds
+    const int cnt = min(FRAMES_CHUNK, N - p0);                             // positions of this chunk
+    const int f = min(max(a.frames[slot], 0), a.F - 1);                    // a bad id gives wrong data, not a wild access
+    const int *off = cloud ? a.off2 : a.off1;
+    const long long start = off[f];
+    const int n = min(max(off[f + 1] - off[f], 1), N);                     // a too-small nmax truncates the frame
+    const size_t sN = (size_t)slot * N + p0;                               // the chunk's first position in a (B,N) tensor
+    const long long last = max(off[a.F] - 1, 0);                           // an empty frame in the offsets reads a neighbour's row, not past the table
+    const auto row_of = [&](int j) { return (size_t)min(start + (p0 + j < n ? p0 + j : 0), last); };
+    if (cloud == 0) {
+        const float *tab = a.tab1;
+        if (t < cnt) {
+            const float *row = tab + row_of(t) * DRAW_COLS1;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {                                  // (B,3,N): coordinates and features
+                const size_t o = ((size_t)slot * 3 + c) * N + p0 + t;
+                a.pc1[o] = row[c];
+                a.ft1[o] = row[3 + c];
+            }
+            a.fg_mask[sN + t] = row[9];                                    // (B,N)
+            a.radar_u[sN + t] = row[10];
+            a.radar_v[sN + t] = row[11];
+        }
+        for (int e = t; e < 3 * cnt; e += FRAMES_CHUNK) {                  // (B,N,3): labels
+            const int j = e / 3, c = e - 3 * j;
+            a.flow_label[3 * sN + e] = tab[row_of(j) * DRAW_COLS1 + 6 + c];
+        }
+        for (int e = t; e < 2 * cnt; e += FRAMES_CHUNK)                    // (B,N,2): optical flow
+            a.opt_flow[2 * sN + e] = tab[row_of(e >> 1) * DRAW_COLS1 + 12 + (e & 1)];
+        if (chunk == 0) {
+            if (t < 16) a.gt_trans[(size_t)slot * 16 + t] = a.trans[(size_t)f * 16 + t];
+            if (t == 0) {
+                a.interval_out[slot] = a.interval[f];
+                a.n1[slot] = n;
+            }
+        }
+    } else {
+        if (t < cnt) {
+            const float *row = a.tab2 + row_of(t) * DRAW_COLS2;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const size_t o = ((size_t)slot * 3 + c) * N + p0 + t;
+                a.pc2[o] = row[c];
+                a.ft2[o] = row[3 + c];
+            }
+        }
+        if (chunk == 0 && t == 0) a.n2[slot] = n;
+    }
+}
+
 }  // namespace
 
 extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2, const int *off1,
@@ -158,5 +231,21 @@ extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, c
                pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, idx1, idx2};
     const int threads = P >= 4096 ? DRAW_THREADS_LARGE : DRAW_THREADS_SMALL;
     hipLaunchKernelGGL(draw_batch_kernel, dim3(B, 2), dim3(threads), lds, (hipStream_t)stream, a);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_draw_frames(int B, int nmax1, int nmax2, int nframes, const float *tab1, const float *tab2, const int *off1,
+                               const int *off2, const float *trans, const float *interval, const int *frames,
+                               float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                               float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *n1, int *n2, void *stream)
+{
+    CMF_CHECK_ARG(B >= 1 && B <= 65535 && nframes >= 1);                   // B is the grid's z extent
+    CMF_CHECK_ARG(nmax1 >= 1 && nmax1 <= CMF_DRAW_MAX_NPOINTS && nmax2 >= 1 && nmax2 <= CMF_DRAW_MAX_NPOINTS);
+    CMF_CHECK_ARG(tab1 && tab2 && off1 && off2 && trans && interval && frames);
+    CMF_CHECK_ARG(pc1 && pc2 && ft1 && ft2 && gt_trans && flow_label && fg_mask && interval_out && radar_u && radar_v && opt_flow && n1 && n2);
+    FramesArgs a{B, nmax1, nmax2, nframes, tab1, tab2, off1, off2, trans, interval, frames,
+                 pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, n1, n2};
+    const int chunks = (std::max(nmax1, nmax2) + FRAMES_CHUNK - 1) / FRAMES_CHUNK;
+    hipLaunchKernelGGL(draw_frames_kernel, dim3(chunks, 2, B), dim3(FRAMES_CHUNK), 0, (hipStream_t)stream, a);
     return cmf_launch_status();
 }

@@ -2,8 +2,8 @@
 (vodDataset :14-137; format described in src/GETTING_STARTED.md:97-106), of ``dataset/vod_clip.py`` (vodClipDataset
 :14-198, the mini-clip loader CMFlow-T trains on) and of ``extract_data_info`` / ``extract_data_info_clip``
 (main_util.py:21-36, clip_util.py:81-96); ``collate_ragged`` / ``extract_data_info_ragged`` batch the evaluation-mode items (whole
-frames of their own sizes) for ``CMFlow.forward_ragged``; ``DeviceSplit`` keeps a whole training split on the device and draws
-each step's batch there (``cmf_draw_batch``).
+frames of their own sizes) for ``CMFlow.forward_ragged``; ``DeviceSplit`` keeps a whole split on the device and draws each step's
+batch there: resampled to ``num_points`` (``cmf_draw_batch``) or as whole frames in a ragged batch (``cmf_draw_frames``).
 
 One sample = one JSON file ``<root>/<partition>/<clip>/<k>_*.json`` with
     pc1, pc2          [n][5]  x, y, z, RCS, v_r          (features fed to the net: [v_r, RCS, RCS], vod.py:62-63)
@@ -232,10 +232,42 @@ DRAW_MAX_POINTS = 16384          # CMF_DRAW_MAX_POINTS of include/cmflow_hip.h: 
 _MASK64 = (1 << 64) - 1
 
 
+def ragged_batches(n1, order, batch_size, bucket=1, drop_last=False):
+    """Cut a frame order into the frame-id lists of ragged batches (host only).  ``n1``: cloud-1 point count per frame id;
+    ``order``: frame ids in visiting order.  ``bucket = 1``: consecutive batches of ``order``.  ``bucket = k > 1``: ``order`` is cut
+    into windows of ``k * batch_size`` frames, every window is sorted by (n1, frame id) and then cut into consecutive batches -- a
+    ragged batch pays for its largest frame, and among the ways to split a window into groups of equal size, consecutive groups of
+    the sorted window have the smallest sum of maxima.  ``drop_last`` drops the tail of ``order`` that does not fill a batch (the
+    frames a DataLoader with drop_last would drop), before any sorting."""
+    batch_size, bucket = int(batch_size), int(bucket)
+    if batch_size < 1 or bucket < 1:
+        raise ValueError("ragged_batches: batch_size and bucket are at least 1")
+    order = [int(f) for f in order]
+    if drop_last:
+        order = order[:len(order) // batch_size * batch_size]
+    out = []
+    for w in range(0, len(order), bucket * batch_size):
+        window = order[w:w + bucket * batch_size]
+        if bucket > 1:
+            window = sorted(window, key=lambda f: (int(n1[f]), f))
+        out += [window[i:i + batch_size] for i in range(0, len(window), batch_size)]
+    return out
+
+
+def padding_share(n1, batches):
+    """The share of padded cloud-1 positions over the batches of ``ragged_batches``: 1 - sum n1 / sum (B * Nmax1)."""
+    valid = sum(int(n1[f]) for b in batches for f in b)
+    padded = sum(len(b) * max(int(n1[f]) for f in b) for b in batches)
+    return 1.0 - valid / padded
+
+
 class DeviceSplit:
-    """A training split decoded once and kept on the device as whole frames; every step's batch is then produced there by one
-    kernel (``cmf_draw_batch``: frame choice, the reference's per-frame resampling to ``npoints``, the layout of
-    extract_data_info) -- no workers, no per-step host work, no per-step host-to-device copy.
+    """A split decoded once and kept on the device as whole frames; every step's batch is then produced there by one kernel --
+    ``cmf_draw_batch`` (``draw``, ``epoch``, ``epoch_clips``: frame choice, the reference's per-frame resampling to ``npoints``, the
+    layout of extract_data_info) or ``cmf_draw_frames`` (``draw_frames``, ``epoch_ragged``, ``sweep``: the frames themselves as a
+    ragged batch, collate_ragged's padding, the layout of extract_data_info_ragged) -- no workers, no per-step host work, no
+    per-step host-to-device copy (``draw_frames`` with ids given on the host copies those ids; the iterators send an epoch's ids
+    once).
 
     Packed CSR-style over F frames: ``tab1`` (sum n1, 14) float32 per point of cloud 1 = xyz 3 | features 3 | label 3 | mask |
     radar_u | radar_v | opt_flow 2; ``tab2`` (sum n2, 6) = xyz 3 | features 3; ``off1``, ``off2`` (F+1) int32; ``trans`` (F,16);
@@ -249,6 +281,16 @@ class DeviceSplit:
         self.max_points = int(max_points)
         self.clips = clips
         self.device = tab1.device
+        self._counts = None
+
+    @property
+    def counts_host(self):
+        """(n1, n2): the point counts of every frame as two numpy int32 arrays, from off1 / off2 -- brought to the host on first use
+        (one device-to-host copy per split) and kept."""
+        if self._counts is None:
+            off = torch.stack((self.off1, self.off2)).cpu().numpy()
+            self._counts = (np.diff(off[0]).astype(np.int32), np.diff(off[1]).astype(np.int32))
+        return self._counts
 
     def __len__(self):
         return self.off1.numel() - 1
@@ -347,6 +389,98 @@ class DeviceSplit:
         for step in range(steps):
             f0 = first[step * batch_size:(step + 1) * batch_size]
             yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j) for j in range(L)]
+
+    # ---- whole frames as ragged batches (cmf_draw_frames) ---------------------------------------------------------------------------
+    def _need_gpu(self, what):
+        if not self.tab1.is_cuda:
+            raise RuntimeError("DeviceSplit.%s: the split is on %s; batches are drawn on the GPU only (no CPU fallback)" % (what, self.device))
+
+    def draw_frames(self, frames, nmax1=None, nmax2=None):
+        """One ragged batch of WHOLE frames: slot s holds frame ``frames[s]``, cloud 1 (and everything indexed by its points) padded
+        to ``nmax1``, cloud 2 to ``nmax2`` with the frame's first point -- bit for bit what
+        as_batch_dict_ragged(extract_data_info_ragged(collate_ragged(items))) gives for the same frames when the two sizes are the
+        batch maxima.  ``frames`` on the host (a sequence of ids): the sizes default to the batch maxima (from counts_host) and a
+        given size smaller than one of the frames raises ValueError.  ``frames`` a device tensor: nothing is read back (but
+        counts_host, once per split, when a size is left out); the sizes default to the split-wide maxima per cloud, and a frame
+        larger than a given size is truncated (``n1`` / ``n2`` say so).  Ids outside the split are clamped to its first / last frame.
+        -> the dict of as_batch_dict_ragged plus ``frames`` (B,) int32 on the device, the (clamped) frame of every slot."""
+        from . import _lib
+        self._need_gpu("draw_frames")
+        on_device = torch.is_tensor(frames) and frames.is_cuda
+        # Errors: a size given on the host that is too small for a frame known on the host is this function's ValueError; B = 0
+        # and a size outside [1, CMF_DRAW_MAX_NPOINTS] are left to the entry point (its argument error -> RuntimeError), so that
+        # both kinds of id argument fail the same way.
+        if on_device:
+            if nmax1 is None or nmax2 is None:
+                c1, c2 = self.counts_host
+                nmax1, nmax2 = (int(c1.max()) if nmax1 is None else nmax1), (int(c2.max()) if nmax2 is None else nmax2)
+        else:
+            ids = np.clip(np.asarray(frames, dtype=np.int64).reshape(-1), 0, len(self) - 1)
+            if ids.size:                                            # an empty batch: any size will do, the entry point refuses B = 0
+                c1, c2 = self.counts_host
+                m1, m2 = int(c1[ids].max()), int(c2[ids].max())
+                for given, need in ((nmax1, m1), (nmax2, m2)):
+                    if given is not None and 1 <= int(given) < need:
+                        raise ValueError("DeviceSplit.draw_frames: nmax1 = %s, nmax2 = %s, but the batch has frames of %d / %d points"
+                                         % (nmax1, nmax2, m1, m2))
+            else:
+                m1 = m2 = 1
+            nmax1, nmax2 = (m1 if nmax1 is None else nmax1), (m2 if nmax2 is None else nmax2)
+        frames = torch.as_tensor(frames, dtype=torch.int32, device=self.device).reshape(-1).clamp(0, len(self) - 1)
+        B, N1, N2 = int(frames.numel()), int(nmax1), int(nmax2)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        out = dict(zip(self.KEYS, (f32(B, 3, N1), f32(B, 3, N2), f32(B, 3, N1), f32(B, 3, N2), f32(B, 4, 4), f32(B, N1, 3), f32(B, N1),
+                                   f32(B), f32(B, N1), f32(B, N1), f32(B, N1, 2))))
+        out["n1"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        out["n2"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        out["frames"] = frames
+        fp, ip = (lambda t: _lib.dev_ptr(t, torch.float32)), (lambda t: _lib.dev_ptr(t, torch.int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().cmf_draw_frames(
+                B, N1, N2, len(self), fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans), fp(self.interval),
+                ip(frames), *(fp(out[k]) for k in self.KEYS), ip(out["n1"]), ip(out["n2"]), _lib.stream_ptr()), "cmf_draw_frames")
+        return out
+
+    def draw_frame_batches(self, batches):
+        """``draw_frames`` for a list of frame-id lists known in advance (an epoch, a sweep, a schedule): all ids go to the device
+        here, in ONE asynchronous copy from pinned memory; every batch is then a slice of that tensor with its sizes -- the batch
+        maxima -- taken from counts_host, so a step costs launches only and the host never waits for the stream.  An iterator of
+        the batch dicts of ``draw_frames``, bit for bit what ``draw_frames(batch)`` returns for each list."""
+        self._need_gpu("draw_frame_batches")
+        batches = [[int(f) for f in b] for b in batches]
+        flat = np.clip(np.array([f for b in batches for f in b], dtype=np.int64), 0, len(self) - 1)
+        ids = torch.from_numpy(flat.astype(np.int32)).pin_memory().to(self.device, non_blocking=True) if flat.size else None
+        return self._draw_frame_batches(batches, flat, ids)
+
+    def _draw_frame_batches(self, batches, flat, ids):
+        c1, c2 = self.counts_host
+        first = 0
+        for b in batches:
+            own = flat[first:first + len(b)]
+            if len(b):
+                yield self.draw_frames(ids[first:first + len(b)], int(c1[own].max()), int(c2[own].max()))
+            else:
+                yield self.draw_frames(b)                              # the entry point's argument error
+            first += len(b)
+
+    def epoch_ragged(self, batch_size, seed, epoch, bucket=1, drop_last=True):
+        """One pass over the whole frames in the shuffled order of ``epoch`` (``_order``, seeded by (seed, epoch); brought to the host
+        once), cut by ``ragged_batches`` (``bucket`` > 1: size bucketing inside windows of bucket * batch_size frames) and sent back
+        once (``draw_frame_batches``): an iterator of the batch dicts of ``draw_frames``, which TrainStep.step_ragged takes as they
+        are.  After the first batch nothing moves between host and device but launches."""
+        self._need_gpu("epoch_ragged")
+        return self.draw_frame_batches(ragged_batches(self.counts_host[0], self._order(len(self), seed, epoch).tolist(), batch_size,
+                                                      bucket, drop_last))
+
+    def sweep(self, batch_size, sort_by_size=False):
+        """Every frame once, no randomness -- the evaluation iterator: in frame order, or sorted by (n1, frame id) so that a batch
+        holds frames of similar size, cut into consecutive batches (the last one may be short).  An iterator of the batch dicts of
+        ``draw_frames`` (through ``draw_frame_batches``: one copy of the ids per sweep); ``batch["frames"]`` says which frames a
+        batch holds."""
+        self._need_gpu("sweep")
+        n1 = self.counts_host[0]
+        order = sorted(range(len(self)), key=lambda f: (int(n1[f]), f)) if sort_by_size else range(len(self))
+        return self.draw_frame_batches(ragged_batches(n1, order, batch_size))
 
 
 def write_sample(path, pc1, pc2, gt_labels, pse_labels, gt_mask, pse_mask, trans, opt_flow=None, radar_u=None, radar_v=None):

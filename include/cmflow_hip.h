@@ -782,6 +782,24 @@ int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float 
                    float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
                    float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream);
 
+/* cmf_draw_frames: B WHOLE frames of the same packed split as one ragged batch (DeviceSplit.draw_frames) -- no sampling, the
+ *   padding rule of dataset.collate_ragged and the layout of extract_data_info_ragged in one launch, one workgroup per (chunk of 256
+ *   positions, cloud, slot).  Tables, offsets, trans, interval and frames as cmf_draw_batch.
+ *   -> pc1, ft1 (B,3,nmax1); pc2, ft2 (B,3,nmax2); gt_trans (B,4,4); flow_label (B,nmax1,3); fg_mask, radar_u, radar_v (B,nmax1);
+ *   interval_out (B); opt_flow (B,nmax1,2); n1, n2 (B) int32: the point counts of the slot's frame.
+ *   Every float is a copy: position j < n of a slot is table row j of its frame, position j >= n is table row 0 (the frame's first
+ *   point with its label, mask, u, v and flow row) -- with nmax1, nmax2 the largest counts of the batch this is, bit for bit, what
+ *   as_batch_dict_ragged(extract_data_info_ragged(collate_ragged(items))) gives for the same frames.
+ *   nmax1, nmax2 <= CMF_DRAW_MAX_NPOINTS; CMF_DRAW_MAX_POINTS does not bound them (nothing is sorted, no LDS is used).  B <= 65535.
+ *   Frame ids and offsets are trusted; ids are clamped to [0, nframes-1] and a frame's count to [1, nmax] inside the kernel, and
+ *   n1, n2 receive the clamped count: a bad id or a too-small nmax gives wrong data, not an access outside the tables.  Offsets
+ *   are expected to describe frames of at least one row (DeviceSplit.from_items refuses empty ones); should one be empty all the
+ *   same, its count is 1 and the row read is clamped to the table's last row, off[nframes] - 1. */
+int cmf_draw_frames(int B, int nmax1, int nmax2, int nframes, const float *tab1, const float *tab2, const int *off1,
+                    const int *off2, const float *trans, const float *interval, const int *frames,
+                    float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                    float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *n1, int *n2, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
