@@ -3,7 +3,8 @@
 // layout (main_util.py:21-36 extract_data_info) in ONE launch.  One workgroup per (slot, cloud).
 //
 // Sampling contract (include/cmflow_hip.h, DESIGN.md "Device-resident split"): Philox4x32-10, keyed per call from (seed, draw),
-// counter (slot, cloud, i, 0), word 0 of the output.
+// counter (slot0 + slot, cloud, i, 0), word 0 of the output (slot0 = 0 for cmf_draw_batch; cmf_draw_batch_at: the local batch is
+// slots slot0 .. slot0 + B - 1 of a larger one, every index into frames and outputs stays local).
 //   n <  N: points 0 .. n-1 in order, then N - n independent draws mulhi(u32, n)                          -- no sort;
 //   n >= N: point i carries the 64-bit key (u32 << 32) | i; the keys go to LDS, padded with maximal keys to the next power of two,
 //           a bitonic sort puts them in ascending order and the low words of the first N are the draw (a uniformly random
@@ -50,6 +51,7 @@ __host__ __device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32
 
 struct DrawArgs {
     int B, N, F, max_points;
+    int slot0;                                                             // counter word 0 of local slot s is slot0 + s
     const float *tab1, *tab2;
     const int *off1, *off2;
     const float *trans, *interval;
@@ -65,6 +67,7 @@ __global__ __launch_bounds__(DRAW_THREADS_LARGE) void draw_batch_kernel(const Dr
     int *sel = reinterpret_cast<int *>(draw_keys);
     const int slot = blockIdx.x, cloud = blockIdx.y, t = threadIdx.x, nt = blockDim.x;
     const int N = a.N;
+    const uint32_t cslot = (uint32_t)(a.slot0 + slot);                     // the generator's slot; every index below uses the local one
     const int f = min(max(a.frames[slot], 0), a.F - 1);                    // a bad id gives wrong data, not a wild access
     const int *off = cloud ? a.off2 : a.off1;
     const long long start = off[f];
@@ -73,14 +76,14 @@ __global__ __launch_bounds__(DRAW_THREADS_LARGE) void draw_batch_kernel(const Dr
     if (n < N) {
         sh = 0;
         for (int j = t; j < N; j += nt)
-            sel[j] = j < n ? j : (int)draw_mulhi(philox4x32_10(slot, cloud, j - n, 0u, a.k0, a.k1).x, (uint32_t)n);
+            sel[j] = j < n ? j : (int)draw_mulhi(philox4x32_10(cslot, cloud, j - n, 0u, a.k0, a.k1).x, (uint32_t)n);
         __syncthreads();
     } else {
         sh = 1;                                                            // low word of key j (little endian)
         int P = 1;
         while (P < n) P <<= 1;
         for (int i = t; i < P; i += nt)
-            draw_keys[i] = i < n ? ((unsigned long long)philox4x32_10(slot, cloud, i, 0u, a.k0, a.k1).x << 32) | (unsigned)i : ~0ull;
+            draw_keys[i] = i < n ? ((unsigned long long)philox4x32_10(cslot, cloud, i, 0u, a.k0, a.k1).x << 32) | (unsigned)i : ~0ull;
         __syncthreads();
         for (int k = 2; k <= P; k <<= 1)
             for (int j = k >> 1; j > 0; j >>= 1) {
@@ -205,12 +208,13 @@ __global__ __launch_bounds__(FRAMES_CHUNK) void draw_frames_kernel(const FramesA
 
 }  // namespace
 
-extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2, const int *off1,
-                              const int *off2, const float *trans, const float *interval, const int *frames,
-                              unsigned long long seed, unsigned long long draw,
-                              float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
-                              float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream)
+extern "C" int cmf_draw_batch_at(int slot0, int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2,
+                                 const int *off1, const int *off2, const float *trans, const float *interval, const int *frames,
+                                 unsigned long long seed, unsigned long long draw,
+                                 float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                                 float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream)
 {
+    CMF_CHECK_ARG(slot0 >= 0 && B >= 1 && (long long)slot0 + B <= 2147483647LL);
     CMF_CHECK_ARG(B >= 1 && npoints >= 1 && npoints <= CMF_DRAW_MAX_NPOINTS && nframes >= 1);
     CMF_CHECK_ARG(max_points >= 1 && max_points <= CMF_DRAW_MAX_POINTS);
     CMF_CHECK_ARG(tab1 && tab2 && off1 && off2 && trans && interval && frames);
@@ -227,11 +231,21 @@ extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, c
         attr_set.done(attr_dev);
     }
     const Philox key = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), 0u, 0u);
-    DrawArgs a{B, npoints, nframes, max_points, tab1, tab2, off1, off2, trans, interval, frames, key.x, key.y,
+    DrawArgs a{B, npoints, nframes, max_points, slot0, tab1, tab2, off1, off2, trans, interval, frames, key.x, key.y,
                pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, idx1, idx2};
     const int threads = P >= 4096 ? DRAW_THREADS_LARGE : DRAW_THREADS_SMALL;
     hipLaunchKernelGGL(draw_batch_kernel, dim3(B, 2), dim3(threads), lds, (hipStream_t)stream, a);
     return cmf_launch_status();
+}
+
+extern "C" int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2, const int *off1,
+                              const int *off2, const float *trans, const float *interval, const int *frames,
+                              unsigned long long seed, unsigned long long draw,
+                              float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                              float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream)
+{
+    return cmf_draw_batch_at(0, B, npoints, nframes, max_points, tab1, tab2, off1, off2, trans, interval, frames, seed, draw,
+                             pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, idx1, idx2, stream);
 }
 
 extern "C" int cmf_draw_frames(int B, int nmax1, int nmax2, int nframes, const float *tab1, const float *tab2, const int *off1,

@@ -254,6 +254,27 @@ def ragged_batches(n1, order, batch_size, bucket=1, drop_last=False):
     return out
 
 
+def _rank_of(what, rank, world):
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("%s: rank %d of a world of %d" % (what, rank, world))
+    return rank, world
+
+
+def shard_batches(batches, rank, world):
+    """Rank ``rank``'s contiguous slice of every GLOBAL frame-id list (host only) -- ``dp.shard_batch``'s rule, DataParallel's
+    scatter, for id lists.  A list whose length is not a multiple of ``world`` is split as evenly as possible: the first
+    ``len % world`` ranks get one id more, so a rank's share may be empty (a list shorter than ``world``).  The shares of the ranks
+    0 .. world-1, in that order, concatenate to the list."""
+    rank, world = _rank_of("shard_batches", rank, world)
+    out = []
+    for b in batches:
+        q, r = divmod(len(b), world)
+        first = rank * q + min(rank, r)
+        out.append([int(f) for f in b[first:first + q + (rank < r)]])
+    return out
+
+
 def padding_share(n1, batches):
     """The share of padded cloud-1 positions over the batches of ``ragged_batches``: 1 - sum n1 / sum (B * Nmax1)."""
     valid = sum(int(n1[f]) for b in batches for f in b)
@@ -337,10 +358,14 @@ class DeviceSplit:
         clips = [tuple(c["index"]) for c in ds.clips_info] if isinstance(ds, vodClipDataset) else None
         return cls.from_items((ds[i] for i in range(len(ds))), device, clips)
 
-    def draw(self, frames, npoints, seed, draw):
+    shard_batches = staticmethod(shard_batches)
+
+    def draw(self, frames, npoints, seed, draw, slot0=0):
         """One batch: slot s holds frame ``frames[s]`` resampled to ``npoints`` as ``dataset._resample`` does (n < npoints: all n
         points in order, then uniform duplicates; n >= npoints: a uniformly random subset in uniformly random order), generator
-        Philox4x32-10 keyed by (seed, draw) -- a slot's result depends on (seed, draw, slot, frame) only.
+        Philox4x32-10 keyed by (seed, draw) -- a slot's result depends on (seed, draw, slot, frame) only.  ``slot0``: the batch is
+        slots ``slot0 .. slot0 + B - 1`` of a larger (global) one -- row s is then, bit for bit, row ``slot0 + s`` of the draw of
+        that whole batch, which is how a data-parallel rank draws its share (``cmf_draw_batch_at``).
         -> the dict of as_batch_dict plus ``idx1``, ``idx2`` (B, npoints) int32, the drawn point of every position."""
         from . import _lib
         if not self.tab1.is_cuda:
@@ -354,10 +379,10 @@ class DeviceSplit:
         out["idx2"] = torch.empty((B, N), dtype=torch.int32, device=self.device)
         fp, ip = (lambda t: _lib.dev_ptr(t, torch.float32)), (lambda t: _lib.dev_ptr(t, torch.int32))
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().cmf_draw_batch(
-                B, N, len(self), self.max_points, fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans),
+            _lib.check(_lib.lib().cmf_draw_batch_at(
+                int(slot0), B, N, len(self), self.max_points, fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans),
                 fp(self.interval), ip(frames), int(seed) & _MASK64, int(draw) & _MASK64, *(fp(out[k]) for k in self.KEYS),
-                ip(out["idx1"]), ip(out["idx2"]), _lib.stream_ptr()), "cmf_draw_batch")
+                ip(out["idx1"]), ip(out["idx2"]), _lib.stream_ptr()), "cmf_draw_batch_at")
         return out
 
     def _order(self, count, seed, epoch):
@@ -365,19 +390,36 @@ class DeviceSplit:
         g.manual_seed((int(seed) * 0x9E3779B97F4A7C15 + int(epoch)) & _MASK64)
         return torch.randperm(count, generator=g, device=self.device)
 
-    def epoch(self, batch_size, npoints, seed, epoch, drop_last=True):
+    @staticmethod
+    def _equal_steps(what, rank, world, drop_last=True):
+        rank, world = _rank_of(what, rank, world)
+        if world > 1 and not drop_last:
+            raise ValueError("%s: drop_last=False at world = %d -- every step ends in a collective, so the ranks take the same number "
+                             "of steps and the frames that do not fill a global batch are dropped" % (what, world))
+        return rank, world
+
+    def epoch(self, batch_size, npoints, seed, epoch, drop_last=True, rank=0, world=1):
         """One pass over the frames in an order shuffled on the device (torch.randperm, generator seeded by (seed, epoch)): yields
-        one batch dict per step; ``draw`` = epoch * steps_per_epoch + step."""
-        F = len(self)
-        steps = F // batch_size if drop_last else -(-F // batch_size)
+        one batch dict per step; ``draw`` = epoch * steps_per_epoch + step.
+        Data parallel (``rank`` of ``world`` processes, ``batch_size`` per rank): the order is the same on every rank, a step is the
+        global batch of ``G = world * batch_size`` frames, ``steps = F // G``, and rank r draws rows ``r * batch_size ..`` of it with
+        ``slot0 = r * batch_size`` -- the ranks' batches concatenated are, bit for bit, the batches of ``epoch(G, ...)`` in one
+        process, whatever ``world`` is.  ``drop_last=False`` is refused at world > 1 (ValueError)."""
+        rank, world = self._equal_steps("DeviceSplit.epoch", rank, world, drop_last)
+        F, G, at = len(self), world * batch_size, rank * batch_size
+        steps = F // G if drop_last else -(-F // G)
         order = self._order(F, seed, epoch).to(torch.int32)
         for step in range(steps):
-            yield self.draw(order[step * batch_size:(step + 1) * batch_size], npoints, seed, epoch * steps + step)
+            yield self.draw(order[step * G + at:step * G + at + batch_size], npoints, seed, epoch * steps + step, at)
 
-    def epoch_clips(self, batch_size, mini_clip_len, npoints, seed, epoch):
+    def epoch_clips(self, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1):
         """CMFlow-T: mini-clips cut as vodClipDataset cuts them (floor(len / L) per clip, remainder dropped), their order
         shuffled; every step yields a list of L batch dicts -- frame j of every mini-clip of the batch -- which TrainStep takes
-        frame by frame between reset_clip() calls.  The last step holds the mini-clips left over (fewer than batch_size)."""
+        frame by frame between reset_clip() calls.  The last step holds the mini-clips left over (fewer than batch_size).
+        Data parallel (``rank`` of ``world``, ``batch_size`` per rank): as in ``epoch`` -- the same shuffled starts on every rank,
+        global batches of ``world * batch_size`` mini-clips, rank r's rows drawn with ``slot0 = r * batch_size``; at world > 1 the
+        mini-clips that do not fill a global batch are dropped (equal steps on every rank), at world = 1 the short last step stays."""
+        rank, world = _rank_of("DeviceSplit.epoch_clips", rank, world)
         if self.clips is None:
             raise ValueError("DeviceSplit.epoch_clips: no clip ranges (build the split with from_dataset on a vodClipDataset)")
         L = int(mini_clip_len)
@@ -385,10 +427,11 @@ class DeviceSplit:
         if not first:
             return
         first = torch.tensor(first, dtype=torch.int32, device=self.device)[self._order(len(first), seed, epoch)]
-        steps = -(-first.numel() // batch_size)
+        G, at = world * batch_size, rank * batch_size
+        steps = first.numel() // G if world > 1 else -(-first.numel() // G)
         for step in range(steps):
-            f0 = first[step * batch_size:(step + 1) * batch_size]
-            yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j) for j in range(L)]
+            f0 = first[step * G + at:step * G + at + batch_size]
+            yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j, at) for j in range(L)]
 
     # ---- whole frames as ragged batches (cmf_draw_frames) ---------------------------------------------------------------------------
     def _need_gpu(self, what):
@@ -463,24 +506,36 @@ class DeviceSplit:
                 yield self.draw_frames(b)                              # the entry point's argument error
             first += len(b)
 
-    def epoch_ragged(self, batch_size, seed, epoch, bucket=1, drop_last=True):
+    def epoch_ragged(self, batch_size, seed, epoch, bucket=1, drop_last=True, rank=0, world=1):
         """One pass over the whole frames in the shuffled order of ``epoch`` (``_order``, seeded by (seed, epoch); brought to the host
         once), cut by ``ragged_batches`` (``bucket`` > 1: size bucketing inside windows of bucket * batch_size frames) and sent back
         once (``draw_frame_batches``): an iterator of the batch dicts of ``draw_frames``, which TrainStep.step_ragged takes as they
-        are.  After the first batch nothing moves between host and device but launches."""
+        are.  After the first batch nothing moves between host and device but launches.
+        Data parallel (``rank`` of ``world``, ``batch_size`` per rank): ``ragged_batches`` cuts GLOBAL batches of
+        ``world * batch_size`` frames from the order every rank shares, and rank r takes its contiguous slice of each
+        (``shard_batches``); ``drop_last=False`` is refused at world > 1 as in ``epoch``.  ``bucket`` > 1 sorts a window by size before
+        it is cut, which narrows the size band of a global batch, so the ranks' ``Nmax`` -- and with them their step times --
+        are close; nothing else balances the ranks."""
+        rank, world = self._equal_steps("DeviceSplit.epoch_ragged", rank, world, drop_last)
         self._need_gpu("epoch_ragged")
-        return self.draw_frame_batches(ragged_batches(self.counts_host[0], self._order(len(self), seed, epoch).tolist(), batch_size,
-                                                      bucket, drop_last))
+        return self.draw_frame_batches(shard_batches(
+            ragged_batches(self.counts_host[0], self._order(len(self), seed, epoch).tolist(), world * batch_size, bucket, drop_last),
+            rank, world))
 
-    def sweep(self, batch_size, sort_by_size=False):
+    def sweep(self, batch_size, sort_by_size=False, rank=0, world=1):
         """Every frame once, no randomness -- the evaluation iterator: in frame order, or sorted by (n1, frame id) so that a batch
         holds frames of similar size, cut into consecutive batches (the last one may be short).  An iterator of the batch dicts of
         ``draw_frames`` (through ``draw_frame_batches``: one copy of the ids per sweep); ``batch["frames"]`` says which frames a
-        batch holds."""
+        batch holds.
+        Data parallel (``rank`` of ``world``, ``batch_size`` per rank): the list is cut into global batches of
+        ``world * batch_size`` frames and rank r takes its slice of each (``shard_batches``); an empty share -- a last global batch
+        shorter than ``world`` -- is skipped, so the ranks may take different numbers of steps (an evaluation loop holds no
+        collective) and together visit every frame once."""
+        rank, world = _rank_of("DeviceSplit.sweep", rank, world)
         self._need_gpu("sweep")
         n1 = self.counts_host[0]
         order = sorted(range(len(self)), key=lambda f: (int(n1[f]), f)) if sort_by_size else range(len(self))
-        return self.draw_frame_batches(ragged_batches(n1, order, batch_size))
+        return self.draw_frame_batches([b for b in shard_batches(ragged_batches(n1, order, world * batch_size), rank, world) if b])
 
 
 def write_sample(path, pc1, pc2, gt_labels, pse_labels, gt_mask, pse_mask, trans, opt_flow=None, radar_u=None, radar_v=None):

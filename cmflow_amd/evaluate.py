@@ -8,8 +8,13 @@ sums are float64 device tensors and the two transform arrays are filled at the f
 CMFlow-T's test loop is serial in the reference (one frame per forward, the recurrent state carried) but the state is reset at known
 frames, so the runs between two resets are independent: ``clip_test_resets`` restates the reset rule, ``clip_test_schedule`` lays
 ``batch_size`` such runs side by side, and ``eval_split_clips`` steps through them with the state of the still-running ones carried.
+
+Data parallel (``rank``, ``world``, ``group``): every rank evaluates its share of the frames -- its slices of ``sweep``'s global
+batches, or the schedule groups ``g % world == rank`` -- and the sums, the frame count and the two transform arrays are all-reduced
+once each AFTER the loop, so every rank returns the result of the whole split.
 """
 import torch
+import torch.distributed as dist
 
 from . import eval_util as E
 from .cmflow import CMFlow, CMFlow_T
@@ -39,6 +44,14 @@ class _Accumulator:
         self.pre_trans_all[at] = pred_t
         self.frames += B
 
+    def all_reduce(self, group):
+        """The ranks' parts into the whole, on every rank: four all_reduce(SUM).  A frame's rows of the two transform arrays are
+        written by the one rank that evaluated it and are zero elsewhere, so their sum is exact."""
+        frames = torch.tensor([self.frames], dtype=torch.int64, device=self.sum.device)
+        for t in (self.sum, frames, self.gt_trans_all, self.pre_trans_all):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        self.frames = frames
+
     def result(self):
         m = self.sum / self.frames
         pick = lambda keys, first: {k: m[first + i] for i, k in enumerate(keys)}
@@ -46,7 +59,7 @@ class _Accumulator:
                 self.gt_trans_all, self.pre_trans_all)
 
 
-def _check(net, split, what, recurrent):
+def _check(net, split, what, recurrent, rank=0, world=1, group=None):
     if isinstance(net, RaFlow) or not isinstance(net, CMFlow):
         raise NotImplementedError("%s: only CMFlow%s has a ragged-batch forward (RaFlow's SFR module normalises by the padded point "
                                   "count)" % (what, "-T" if recurrent else ""))
@@ -58,10 +71,21 @@ def _check(net, split, what, recurrent):
                          % (what, split.max_points, net.RAGGED_MAX_POINTS))
     if recurrent and split.clips is None:
         raise ValueError("%s: no clip ranges (build the split with from_dataset on a vodClipDataset)" % what)
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("%s: rank %d of a world of %d" % (what, rank, world))
+    if world > 1:
+        if not (dist.is_available() and dist.is_initialized()):
+            raise ValueError("%s: world = %d, but no process group is initialised (the ranks' results are all-reduced at the end)"
+                             % (what, world))
+        if dist.get_world_size(group) != world or dist.get_rank(group) != rank:
+            raise ValueError("%s: rank %d of %d given, the process group says rank %d of %d"
+                             % (what, rank, world, dist.get_rank(group), dist.get_world_size(group)))
     split._need_gpu(what)                                           # every refusal comes before net.eval()
+    return rank, world
 
 
-def eval_split(net, split, batch_size, args=None, sort_by_size=False, on_batch=None):
+def eval_split(net, split, batch_size, args=None, sort_by_size=False, on_batch=None, rank=0, world=1, group=None):
     """eval_one_epoch (main_util.py:93-206) for CMFlow on the whole frames of a DeviceSplit: ``split.sweep`` -> ``forward_ragged`` ->
     ``eval_batch_ragged`` per batch under no_grad, ``B * metric`` summed in float64 on the device and divided by the frame count --
     the per-frame average the reference reports at its test batch size of 1, whatever ``batch_size`` is here.  The frame ids of
@@ -77,16 +101,25 @@ def eval_split(net, split, batch_size, args=None, sort_by_size=False, on_batch=N
     the reference that call is what switches every later training epoch to eval-mode BatchNorm (train_one_epoch never calls
     net.train()), the regime ``TrainStep.step_ragged`` trains in.
     RaFlow raises NotImplementedError (no ragged forward), a split with a frame above ``RAGGED_MAX_POINTS`` ValueError, a split
-    that is not on the GPU RuntimeError -- all before anything is launched and before ``net.eval()``."""
-    _check(net, split, "eval_split", False)
+    that is not on the GPU RuntimeError -- all before anything is launched and before ``net.eval()``.
+
+    Data parallel: rank ``rank`` of ``world`` processes (``batch_size`` per rank; ``group``: their process group, None = the
+    default one) sweeps its share, ``split.sweep(batch_size, sort_by_size, rank, world)``; after the loop -- never inside it -- the
+    float64 sums, the frame count and the two transform arrays are all-reduced (SUM) once each, and every rank returns the
+    result of the whole split: the transform arrays bit for bit those of a single process, the metrics up to the order of a
+    float64 sum.  ``on_batch`` sees the rank's own batches.  ``world`` > 1 without an initialised process group, or a ``rank`` /
+    ``world`` that is not the group's, raises ValueError with the other refusals."""
+    rank, world = _check(net, split, "eval_split", False, rank, world, group)
     net.eval()
     acc = _Accumulator(split, args)
     with torch.no_grad():
-        for batch in split.sweep(batch_size, sort_by_size):
+        for batch in split.sweep(batch_size, sort_by_size, rank, world):
             out = net.forward_ragged(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], batch["n1"], batch["n2"])
             if on_batch is not None:
                 on_batch(batch, out)
             acc.add(batch, out[0], out[2], out[3])
+    if world > 1:
+        acc.all_reduce(group)
     return acc.result()
 
 
@@ -127,23 +160,27 @@ def clip_test_schedule(resets, n_frames, batch_size):
     return groups
 
 
-def eval_split_clips(net, split, batch_size, update_len, args=None, on_batch=None):
+def eval_split_clips(net, split, batch_size, update_len, args=None, on_batch=None, rank=0, world=1, group=None):
     """CMFlow-T's test protocol (test_one_epoch_seq, clip_util.py:182-298) on a DeviceSplit built from a vodClipDataset
     (``split.clips``; ValueError otherwise): every frame once, the recurrent global feature carried from frame to frame and reset
     where ``clip_test_resets(split.clips, len(split), update_len)`` says -- run as ``clip_test_schedule`` lays it out, ``batch_size``
     segments side by side per forward instead of one frame.  Step 0 of a group starts from ``gfeat = None``; a later step takes the
     previous step's state of the segments still running, ``gfeat[:active]``.  As in eval_split the host does not wait for the
     device inside the loop (the frame ids of the whole schedule are sent once).  Accumulation, ``on_batch`` (outputs: the five-tuple of
-    ``CMFlow_T.forward_ragged``), the returned tuple and the ``net.eval()`` call are eval_split's."""
-    _check(net, split, "eval_split_clips", True)
+    ``CMFlow_T.forward_ragged``), the returned tuple and the ``net.eval()`` call are eval_split's.
+    Data parallel (``rank``, ``world``, ``group`` as in eval_split): group g of the schedule -- ``batch_size`` segments, which share
+    no state with any other group -- is run by rank ``g % world``; the final all-reduce is eval_split's."""
+    rank, world = _check(net, split, "eval_split_clips", True, rank, world, group)
     schedule = clip_test_schedule(clip_test_resets(split.clips, len(split), update_len), len(split), batch_size)
+    if world > 1:
+        schedule = schedule[rank::world]
     net.eval()
     acc = _Accumulator(split, args)
     with torch.no_grad():
-        batches = split.draw_frame_batches([step for group in schedule for step in group])      # the ids of the epoch in one copy
-        for group in schedule:
+        batches = split.draw_frame_batches([step for steps in schedule for step in steps])      # the ids of the epoch in one copy
+        for steps in schedule:                                      # one group of the schedule
             gfeat = None
-            for step in group:
+            for step in steps:
                 batch = next(batches)
                 out = net.forward_ragged(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], batch["n1"], batch["n2"],
                                          None if gfeat is None else gfeat[:len(step)])
@@ -151,4 +188,6 @@ def eval_split_clips(net, split, batch_size, update_len, args=None, on_batch=Non
                 if on_batch is not None:
                     on_batch(batch, out)
                 acc.add(batch, out[0], out[2], out[3])
+    if world > 1:
+        acc.all_reduce(group)
     return acc.result()

@@ -782,6 +782,17 @@ int cmf_draw_batch(int B, int npoints, int nframes, int max_points, const float 
                    float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
                    float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream);
 
+/* cmf_draw_batch_at: slots slot0 .. slot0 + B - 1 of a larger (global) batch -- a data-parallel rank's share, DeviceSplit.draw's
+ *   slot0.  The same kernel and arguments as cmf_draw_batch (which is slot0 = 0); local slot s samples with counter
+ *   (slot0 + s, cloud, i, 0) and everything else, frames[s] and every output row, is indexed by the local slot.  So row s equals, bit
+ *   for bit, row slot0 + s of the one call that draws the whole global batch with the same (seed, draw) and the same frame in that
+ *   slot.  slot0 >= 0 and slot0 + B <= INT_MAX, an argument error otherwise. */
+int cmf_draw_batch_at(int slot0, int B, int npoints, int nframes, int max_points, const float *tab1, const float *tab2,
+                      const int *off1, const int *off2, const float *trans, const float *interval, const int *frames,
+                      unsigned long long seed, unsigned long long draw,
+                      float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
+                      float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *idx1, int *idx2, void *stream);
+
 /* cmf_draw_frames: B WHOLE frames of the same packed split as one ragged batch (DeviceSplit.draw_frames) -- no sampling, the
  *   padding rule of dataset.collate_ragged and the layout of extract_data_info_ragged in one launch, one workgroup per (chunk of 256
  *   positions, cloud, slot).  Tables, offsets, trans, interval and frames as cmf_draw_batch.
