@@ -275,6 +275,39 @@ def shard_batches(batches, rank, world):
     return out
 
 
+def sweep_shares(count, batch_size, rank=0, world=1):
+    """The bookkeeping of an in-order pass over ``count`` things (frames, mini-clips) in global batches of
+    ``G = world * batch_size``, the short last batch kept (host only) -> (nbatches, shares): ``nbatches = ceil(count / G)``, and one
+    ``(b, first, last)`` per global batch b of which rank ``rank`` holds something -- its rows ``[b * G + rank * batch_size, ...)`` cut
+    at ``count``.  A rank whose share of the last global batch is empty has no entry for it; the shares of the ranks 0 .. world-1
+    of one b, in that order, are that global batch."""
+    rank, world = _rank_of("sweep_shares", rank, world)
+    count, batch_size = int(count), int(batch_size)
+    if batch_size < 1:
+        raise ValueError("sweep_shares: batch_size is at least 1")
+    G = world * batch_size
+    nbatches = -(-count // G)
+    shares = []
+    for b in range(nbatches):
+        first = b * G + rank * batch_size
+        last = min(first + batch_size, count)
+        if first < last:
+            shares.append((b, first, last))
+    return nbatches, shares
+
+
+def mini_clip_starts(clips, mini_clip_len):
+    """The first frame of every mini-clip as vodClipDataset cuts them (vod_clip.py:40-50): floor(len / L) per clip, in clip order,
+    the remainder of a clip dropped.  ``clips``: [first, last) frame range per clip."""
+    L = int(mini_clip_len)
+    if L < 1:
+        raise ValueError("mini_clip_starts: mini_clip_len is at least 1")
+    return [int(a) + i * L for a, b in clips for i in range((int(b) - int(a)) // L)]
+
+
+SPLIT_FORMAT_VERSION = 1         # DeviceSplit.save / load
+
+
 def padding_share(n1, batches):
     """The share of padded cloud-1 positions over the batches of ``ragged_batches``: 1 - sum n1 / sum (B * Nmax1)."""
     valid = sum(int(n1[f]) for b in batches for f in b)
@@ -288,7 +321,8 @@ class DeviceSplit:
     layout of extract_data_info) or ``cmf_draw_frames`` (``draw_frames``, ``epoch_ragged``, ``sweep``: the frames themselves as a
     ragged batch, collate_ragged's padding, the layout of extract_data_info_ragged) -- no workers, no per-step host work, no
     per-step host-to-device copy (``draw_frames`` with ids given on the host copies those ids; the iterators send an epoch's ids
-    once).
+    once).  ``sweep_resampled`` / ``sweep_clips`` are the validation iterators of a training run (every frame / mini-clip in order,
+    resampled); ``save`` / ``load`` keep the packed split in one file.
 
     Packed CSR-style over F frames: ``tab1`` (sum n1, 14) float32 per point of cloud 1 = xyz 3 | features 3 | label 3 | mask |
     radar_u | radar_v | opt_flow 2; ``tab2`` (sum n2, 6) = xyz 3 | features 3; ``off1``, ``off2`` (F+1) int32; ``trans`` (F,16);
@@ -423,15 +457,86 @@ class DeviceSplit:
         if self.clips is None:
             raise ValueError("DeviceSplit.epoch_clips: no clip ranges (build the split with from_dataset on a vodClipDataset)")
         L = int(mini_clip_len)
-        first = [a + i * L for a, b in self.clips for i in range((b - a) // L)]
+        first = mini_clip_starts(self.clips, L)
         if not first:
             return
-        first = torch.tensor(first, dtype=torch.int32, device=self.device)[self._order(len(first), seed, epoch)]
+        first = self._ids_to_device(first)[self._order(len(first), seed, epoch)]
         G, at = world * batch_size, rank * batch_size
         steps = first.numel() // G if world > 1 else -(-first.numel() // G)
         for step in range(steps):
             f0 = first[step * G + at:step * G + at + batch_size]
             yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j, at) for j in range(L)]
+
+    def _ids_to_device(self, ids):
+        """A host list of frame ids as an int32 device tensor: one asynchronous copy from pinned memory (the host does not wait)."""
+        ids = torch.tensor(ids, dtype=torch.int32)
+        return ids.pin_memory().to(self.device, non_blocking=True) if self.tab1.is_cuda else ids.to(self.device)
+
+    # ---- every frame in index order, resampled: the validation iterators (main.py:206-208) ------------------------------------------
+    def sweep_resampled(self, batch_size, npoints, seed, epoch=0, rank=0, world=1):
+        """The reference's validation loader (main.py:206-208: the training-mode dataset on 'val', ``val_batch_size`` frames per batch,
+        shuffle off, drop_last off): frames 0 .. F-1 in index order, every one resampled to ``npoints`` by ``draw``; the short last
+        batch is kept.  Yields the dict of ``draw`` plus ``frames`` ((B,) int32 on the device), the frame of every row.
+        ``sweep_shares`` does the bookkeeping: global batch b of ``G = world * batch_size`` frames is drawn with
+        ``draw = epoch * nbatches + b`` and rank ``rank`` draws its rows ``b * G + rank * batch_size ..`` with
+        ``slot0 = rank * batch_size`` -- the ranks' batches concatenated are, bit for bit, the batches of
+        ``sweep_resampled(G, ...)`` in one process.  No collective belongs to a step, so the ranks may take different numbers of
+        steps: a rank whose share of the last global batch is empty yields nothing for it.  Nothing is copied to or from the
+        host."""
+        rank, world = _rank_of("DeviceSplit.sweep_resampled", rank, world)
+        self._need_gpu("sweep_resampled")
+        nbatches, shares = sweep_shares(len(self), batch_size, rank, world)
+        ids = torch.arange(len(self), dtype=torch.int32, device=self.device)
+        for b, first, last in shares:
+            batch = self.draw(ids[first:last], npoints, seed, int(epoch) * nbatches + b, rank * int(batch_size))
+            batch["frames"] = ids[first:last]
+            yield batch
+
+    def sweep_clips(self, batch_size, mini_clip_len, npoints, seed, epoch=0, rank=0, world=1):
+        """CMFlow-T's validation loader (vodClipDataset in training mode on 'val', shuffle off, drop_last off): the mini-clips of
+        ``epoch_clips`` (``mini_clip_starts``) in order, ``batch_size`` per step, the short last step kept.  Every step yields a list
+        of L batch dicts -- frame j of every mini-clip of the step, each as ``sweep_resampled`` yields them; frame j of
+        global step s is drawn with ``draw = (epoch * steps + s) * L + j``.  ``rank`` / ``world`` as in ``sweep_resampled``, over
+        mini-clips.  The starts go to the device in one asynchronous copy before the first step."""
+        rank, world = _rank_of("DeviceSplit.sweep_clips", rank, world)
+        if self.clips is None:
+            raise ValueError("DeviceSplit.sweep_clips: no clip ranges (build the split with from_dataset on a vodClipDataset)")
+        self._need_gpu("sweep_clips")
+        L = int(mini_clip_len)
+        starts = mini_clip_starts(self.clips, L)
+        steps, shares = sweep_shares(len(starts), batch_size, rank, world)
+        if not shares:
+            return
+        starts = self._ids_to_device(starts)
+        for s, first, last in shares:
+            step = []
+            for j in range(L):
+                frames = starts[first:last] + j
+                step.append(self.draw(frames, npoints, seed, (int(epoch) * steps + s) * L + j, rank * int(batch_size)))
+                step[-1]["frames"] = frames
+            yield step
+
+    # ---- one file per split ---------------------------------------------------------------------------------------------------------
+    def save(self, path):
+        """The packed split in one ``torch.save`` file (tensors on the CPU): a run, or a resumed one, need not decode a split's JSON
+        files again.  Written to a temporary name and renamed, so a killed process leaves no half file under ``path``."""
+        rec = {"format": "cmflow_amd.DeviceSplit", "version": SPLIT_FORMAT_VERSION, "max_points": self.max_points,
+               "clips": None if self.clips is None else [(int(a), int(b)) for a, b in self.clips]}
+        for k in ("tab1", "tab2", "off1", "off2", "trans", "interval"):
+            rec[k] = getattr(self, k).detach().cpu()
+        tmp = "%s.tmp%d" % (path, os.getpid())
+        torch.save(rec, tmp)
+        os.replace(tmp, path)
+
+    @classmethod
+    def load(cls, path, device):
+        """The split ``save`` wrote, on ``device``.  A file of another format version (or not of this format) raises ValueError."""
+        rec = torch.load(path, map_location="cpu")
+        if not isinstance(rec, dict) or rec.get("format") != "cmflow_amd.DeviceSplit" or rec.get("version") != SPLIT_FORMAT_VERSION:
+            raise ValueError("DeviceSplit.load: %s is not a DeviceSplit file of format version %d (found %r)"
+                             % (path, SPLIT_FORMAT_VERSION, rec.get("version") if isinstance(rec, dict) else type(rec).__name__))
+        clips = None if rec["clips"] is None else [tuple(c) for c in rec["clips"]]
+        return cls(*(rec[k].to(device) for k in ("tab1", "tab2", "off1", "off2", "trans", "interval")), rec["max_points"], clips)
 
     # ---- whole frames as ragged batches (cmf_draw_frames) ---------------------------------------------------------------------------
     def _need_gpu(self, what):

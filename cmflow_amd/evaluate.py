@@ -191,3 +191,110 @@ def eval_split_clips(net, split, batch_size, update_len, args=None, on_batch=Non
     if world > 1:
         acc.all_reduce(group)
     return acc.result()
+
+
+# ---- validation epochs: frames resampled to num_points, in order (train()'s eval_one_epoch / eval_one_epoch_seq) -----------------------
+class _PooledAccumulator(_Accumulator):
+    """_Accumulator for dense batches of resampled frames: one ``eval_batch`` per batch -- the points of the batch pooled, as the
+    reference's metrics do at a validation batch size above 1 (main_util.py:175-192) -- weighted by the batch's frame count."""
+
+    def add(self, batch, pred_f, pred_t, pred_m):
+        B = batch["pc1"].shape[0]
+        groups = E.eval_batch(batch["pc1"], pred_f.transpose(1, 2).contiguous(), batch["flow_label"], batch["fg_mask"], pred_m,
+                              batch["gt_trans"], pred_t, self.args)
+        self.sum = self.sum + B * torch.stack([v for d in groups for v in d.values()])
+        at = batch["frames"].long()
+        self.gt_trans_all[at] = batch["gt_trans"]
+        self.pre_trans_all[at] = pred_t
+        self.frames += B
+
+    def result(self):
+        if not torch.is_tensor(self.frames):                        # a true division by the count (a fill, no copy), as the host's is;
+            self.frames = torch.full((1,), self.frames, dtype=torch.int64, device=self.sum.device)      # by a Python number: * (1 / n)
+        return super().result()
+
+
+def _check_epoch(net, split, what, recurrent, rank, world, group):
+    """The refusals of eval_epoch / eval_epoch_clips, all before ``net.eval()``: the model class, clip ranges, rank / world / group
+    (``_check``'s rules and kinds of errors), the split's device."""
+    if not isinstance(net, CMFlow):
+        raise NotImplementedError("%s: CMFlow, CMFlow_T or RaFlow (got %s)" % (what, type(net).__name__))
+    if isinstance(net, CMFlow_T) != recurrent:
+        raise ValueError("%s takes %s" % (what, "CMFlow_T (its recurrent state is carried along a mini-clip)" if recurrent
+                                          else "CMFlow or RaFlow; CMFlow_T validates on mini-clips: eval_epoch_clips"))
+    if recurrent and split.clips is None:
+        raise ValueError("%s: no clip ranges (build the split with from_dataset on a vodClipDataset)" % what)
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("%s: rank %d of a world of %d" % (what, rank, world))
+    if world > 1:
+        if not (dist.is_available() and dist.is_initialized()):
+            raise ValueError("%s: world = %d, but no process group is initialised (the ranks' results are all-reduced at the end)"
+                             % (what, world))
+        if dist.get_world_size(group) != world or dist.get_rank(group) != rank:
+            raise ValueError("%s: rank %d of %d given, the process group says rank %d of %d"
+                             % (what, rank, world, dist.get_rank(group), dist.get_world_size(group)))
+    split._need_gpu(what)
+    return rank, world
+
+
+def eval_epoch(net, split, batch_size, npoints, seed, epoch=0, args=None, on_batch=None, rank=0, world=1, group=None):
+    """eval_one_epoch as the reference's ``train()`` uses it after every training epoch (main.py:138 on the loader of main.py:206-208):
+    the frames of ``split`` in index order, each resampled to ``npoints`` (``split.sweep_resampled``: ``batch_size`` frames per dense
+    batch, the short last batch kept; the draws keyed by (seed, epoch)), and per batch under no_grad the dense
+    ``net(pc1, pc2, ft1, ft2, None, 'test')`` -- for RaFlow ``net(pc1, pc2, ft1, ft2, interval)`` and its outputs 1..3 -- then one
+    ``eval_util.eval_batch`` (metrics pooled over the batch's points).  ``B_b * metric`` is summed in float64 on the device and
+    divided by the frame count at the end (main_util.py:175-202); both transforms of a frame land at the frame's index.  Inside the loop
+    the host only enqueues.  ``on_batch(batch, outputs)`` as in eval_split.
+    -> the 5-tuple of eval_split.  This is NOT the test protocol (whole frames, per-frame metrics: eval_split); it is the number the
+    reference selects ``model.best.t7`` by.
+
+    Calls ``net.eval()`` and does not restore the mode (see eval_split: this call is what puts CMFlow's later training epochs under
+    eval-mode BatchNorm).  Before that call it refuses: a model that is not CMFlow / RaFlow (NotImplementedError), CMFlow_T
+    (ValueError: eval_epoch_clips), a bad rank / world or a missing process group (ValueError), a split on the CPU (RuntimeError).
+    Data parallel: as eval_split -- every rank sweeps its rows of the global batches, and sums, frame count and transform arrays
+    are all-reduced once each after the loop."""
+    rank, world = _check_epoch(net, split, "eval_epoch", False, rank, world, group)
+    net.eval()
+    acc = _PooledAccumulator(split, args)
+    self_supervised = isinstance(net, RaFlow)
+    with torch.no_grad():
+        for batch in split.sweep_resampled(batch_size, npoints, seed, epoch, rank, world):
+            if self_supervised:                                     # main_util.py:140
+                out = net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], batch["interval"])
+                pred_f, pred_t, pred_m = out[1], out[2], out[3]
+            else:                                                   # main_util.py:142
+                out = net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, 'test')
+                pred_f, pred_t, pred_m = out[0], out[2], out[3]
+            if on_batch is not None:
+                on_batch(batch, out)
+            acc.add(batch, pred_f, pred_t, pred_m)
+    if world > 1:
+        acc.all_reduce(group)
+    return acc.result()
+
+
+def eval_epoch_clips(net, split, batch_size, mini_clip_len, npoints, seed, epoch=0, args=None, on_batch=None, rank=0, world=1,
+                     group=None):
+    """eval_one_epoch_seq (clip_util.py:99-178), CMFlow-T's validation inside ``train()``: the mini-clips of ``split`` in order
+    (``split.sweep_clips``: ``batch_size`` per step, the short last step kept), the L frames of a step one after the other through
+    ``net(pc1, pc2, ft1, ft2, None, 'test', gfeat)`` with ``gfeat = None`` at frame 0 of every step and the returned state carried
+    to the next frame.  Accumulation as in eval_epoch, over the frames evaluated (the frames a clip's remainder leaves out are not
+    visited: their rows of the two transform arrays stay zero, and they do not count).  Everything else -- ``net.eval()``, the
+    refusals (here CMFlow_T is the model it takes; a split without clip ranges: ValueError), ``on_batch``, data parallel -- as
+    eval_epoch."""
+    rank, world = _check_epoch(net, split, "eval_epoch_clips", True, rank, world, group)
+    net.eval()
+    acc = _PooledAccumulator(split, args)
+    with torch.no_grad():
+        for step in split.sweep_clips(batch_size, mini_clip_len, npoints, seed, epoch, rank, world):
+            gfeat = None                                            # clip_util.py:131-134
+            for batch in step:
+                out = net(batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"], None, 'test', gfeat)
+                gfeat = out[4]
+                if on_batch is not None:
+                    on_batch(batch, out)
+                acc.add(batch, out[0], out[2], out[3])
+    if world > 1:
+        acc.all_reduce(group)
+    return acc.result()

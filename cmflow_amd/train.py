@@ -5,10 +5,17 @@
 ``TrainStep`` owns the optimizer (Adam lr 1e-3, weight decay 1e-4: main.py:107), the flat
 gradient bucket and the loss module; ``__call__(batch)`` runs one optimizer step and returns
 (loss, items) as device tensors.
+
+Around the step, on a ``dataset.DeviceSplit``: ``train_epoch`` / ``train_epoch_clips`` are the reference's ``train_one_epoch``
+(main_util.py:39-90) / ``train_one_epoch_seq`` (clip_util.py:20-78) without a host read inside the epoch, and ``fit`` is its
+``train()`` (main.py:104-170): epochs, a validation epoch after each (``evaluate.eval_epoch`` / ``eval_epoch_clips``), StepLR,
+``model.best.t7`` by validation RNE, and a resume point from which a run continues bit for bit.
 """
+import math
 import os
 
 import torch
+import torch.distributed as dist
 
 from . import synth
 from .dp import FlatAdam, FlatGradBucket, SegmentedReducer
@@ -17,8 +24,9 @@ from .losses import RadarFlowLoss, make_labels, make_labels_ragged
 
 
 class TrainStep:
-    def __init__(self, net, vr_thres=0.3, lr=0.001, weight_decay=1e-4, camera_projection=None, t_camera_radar=None):
+    def __init__(self, net, vr_thres=0.3, lr=0.001, weight_decay=1e-4, camera_projection=None, t_camera_radar=None, group=None):
         self.net = net
+        self.group = group                                         # the process group of the gradient all-reduce (None: the default one)
         dev = next(net.parameters()).device
         self.vr_thres = vr_thres
         self.loss_obj = RadarFlowLoss(camera_projection or synth.CAMERA_PROJECTION,
@@ -51,7 +59,7 @@ class TrainStep:
             try:
                 late = [m for m in (enc2, getattr(net, "gru", None), net.fp, net.mp) if m is not None]
                 segs = [self.bucket.segment_of(late), self.bucket.segment_of([net.fc_layer]), self.bucket.segment_of([net.mse_layer])]
-                self.reducer = SegmentedReducer(self.bucket, segs)
+                self.reducer = SegmentedReducer(self.bucket, segs, group)
             except ValueError:                                   # a model whose parameter order does not follow the data flow
                 self.reducer = None
 
@@ -98,7 +106,7 @@ class TrainStep:
         if overlap:
             self.reducer.finish()
         else:
-            self.bucket.all_reduce_mean(force=self.force_allreduce)
+            self.bucket.all_reduce_mean(self.group, force=self.force_allreduce)
         self.opt.step()
         return loss.detach(), items, outs, labels
 
@@ -135,6 +143,239 @@ class TrainStep:
         self.bucket.zero()
         loss.backward()
         join_side_streams()                         # gradient sinks written on side streams (fused_blocks.grad_sink)
-        self.bucket.all_reduce_mean(force=self.force_allreduce)
+        self.bucket.all_reduce_mean(self.group, force=self.force_allreduce)
         self.opt.step()
         return loss.detach(), items, outs, labels
+
+
+# ---- epochs (main_util.py:39-90, clip_util.py:20-78) ---------------------------------------------------------------------------------
+def _epoch_statistics(rows, weights, dev):
+    """rows: per step a (1 + K,) tensor [loss, items...]; weights: the steps' batch sizes (host ints) -> (sum loss * B / sum B, the
+    items' means over the steps), float64 on the device, every sum taken in step order as the reference's host loop takes them."""
+    if not rows:
+        raise ValueError("an epoch without a step: the split holds fewer frames (mini-clips) than one global batch")
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    items = torch.zeros(rows[0].numel() - 1, dtype=torch.float64, device=dev)
+    for row, B in zip(rows, weights):
+        row = row.double()
+        total = total + row[0] * B
+        items = items + row[1:]
+    return total / _count(sum(weights), dev), items / _count(len(rows), dev)
+
+
+def _count(n, dev):
+    """n as a 0-d float64 device tensor (a fill, no copy): dividing by it is a true division, as the reference's host arithmetic
+    is -- dividing a device tensor by a Python number multiplies by the rounded reciprocal."""
+    return torch.full((), float(n), dtype=torch.float64, device=dev)
+
+
+def train_epoch(step, split, batch_size, npoints, seed, epoch, rank=0, world=1):
+    """train_one_epoch (main_util.py:39-90) for CMFlow / RaFlow: ``step`` (a TrainStep) on every batch of
+    ``split.epoch(batch_size, npoints, seed, epoch, drop_last=True, rank, world)`` -- the reference's shuffled loader with drop_last
+    (main.py:207).  -> (total_loss, loss_items): ``total_loss = sum loss * B / sum B`` and, per key of the step's items, the mean
+    over the steps, as 0-d float64 device tensors (the reference takes the same sums of ``.item()`` values on the host, in float64;
+    here they are taken in step order, which is numpy's order below 8 steps and differs from its pairwise order in the last
+    bits above).  Inside the loop the host only enqueues: nothing is read back, so it never waits for the device.
+    Like the reference it does NOT touch ``net.training``: whoever called ``net.eval()`` last decides the BatchNorm regime (``fit``).
+    At world > 1 the statistics are this rank's own (``fit`` averages them over the ranks once per epoch)."""
+    rows, weights = [], []
+    for batch in split.epoch(batch_size, npoints, seed, epoch, True, rank, world):
+        loss, items = step(batch)[:2]
+        rows.append(torch.stack([loss, *items.values()]))
+        weights.append(int(batch["pc1"].shape[0]))
+        keys = list(items)
+    total, means = _epoch_statistics(rows, weights, split.device)
+    return total, {k: means[i] for i, k in enumerate(keys)}
+
+
+def train_epoch_clips(step, split, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1):
+    """train_one_epoch_seq (clip_util.py:20-78) for CMFlow_T over ``split.epoch_clips(...)``: ``net.train()`` at entry (:25 -- unlike
+    train_one_epoch, so CMFlow-T trains every epoch under train-mode BatchNorm), then per step ``step.reset_clip()`` and one
+    optimizer step per frame of the mini-clips, the recurrent state carried (detached) from frame to frame.  A step's loss is the
+    float32 mean over its L frames (:64,68), its items the float64 means over the frames (:70); ``total_loss`` weights the steps by
+    their number of mini-clips (the last step of ``epoch_clips`` may be short at world = 1) and the items are averaged over the
+    steps (:71-76).  Returns and the no-read-back rule as in train_epoch."""
+    step.net.train()
+    L = int(mini_clip_len)
+    rows, weights = [], []
+    for clip in split.epoch_clips(batch_size, L, npoints, seed, epoch, rank, world):
+        step.reset_clip()
+        frames = []
+        for batch in clip:
+            loss, items = step(batch)[:2]
+            frames.append((loss, torch.stack(list(items.values()))))
+            keys = list(items)
+        iter_loss = frames[0][0]
+        iter_items = frames[0][1].double()
+        for loss, vals in frames[1:]:
+            iter_loss = iter_loss + loss
+            iter_items = iter_items + vals.double()
+        rows.append(torch.cat(((iter_loss / L).double().reshape(1), iter_items / _count(L, split.device))))
+        weights.append(int(clip[0]["pc1"].shape[0]))
+    total, means = _epoch_statistics(rows, weights, split.device)
+    return total, {k: means[i] for i, k in enumerate(keys)}
+
+
+# ---- the run (main.py:104-170) -------------------------------------------------------------------------------------------------------
+BEST_FILE = os.path.join("models", "model.best.t7")               # main.py:147-149, under out_dir
+LAST_FILE = "last.pt"
+RESUME_VERSION = 1
+
+
+def make_schedule(opt, decay_epochs, decay_rate):
+    """The reference's schedule (main.py:108): torch's own StepLR on the step's optimizer, stepped once per epoch.  The scheduler
+    itself and not ``lr * decay_rate ** (epoch // decay_epochs)``: it multiplies the current rate by gamma at every decay, and
+    that recursive product differs from the closed form in the last bits."""
+    return torch.optim.lr_scheduler.StepLR(opt, int(decay_epochs), gamma=float(decay_rate))
+
+
+def replaces_best(best, score):
+    """main.py:143: ``best_val_res >= eval_score`` -- a tie replaces the kept model, a NaN score never does."""
+    return bool(best >= score)
+
+
+def save_atomic(obj, path):
+    """torch.save to a temporary name in the same directory, then os.replace: a killed run leaves the previous whole file."""
+    tmp = "%s.tmp%d" % (path, os.getpid())
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def _broadcast_buffers(net, group):
+    """Rank 0's buffers (the BatchNorm running statistics and counters) to every rank.  The parameters are identical on all ranks
+    (one averaged gradient), the running statistics are each rank's own; nn.DataParallel keeps those of its first replica
+    (models/model.py:40-42), and so does this -- once per epoch, before the validation, so that all ranks validate, and go on
+    training, the same network, the one rank 0 writes to disk."""
+    src = 0 if group is None else dist.get_global_rank(group, 0)
+    for t in net.buffers():
+        dist.broadcast(t.data, src=src, group=group)
+
+
+def _refuse(net, train_split, val_split, epochs, rank, world, group):
+    """fit's refusals, before anything is launched, built or switched."""
+    from .cmflow import CMFlow_T
+    from .evaluate import _check_epoch
+    if int(epochs) < 1:
+        raise ValueError("fit: epochs = %d; at least one" % int(epochs))
+    recurrent = isinstance(net, CMFlow_T)
+    if recurrent and train_split.clips is None:
+        raise ValueError("fit: CMFlow_T trains on mini-clips and the training split has no clip ranges (build it with from_dataset "
+                         "on a vodClipDataset)")
+    rank, world = _check_epoch(net, val_split, "fit", recurrent, rank, world, group)      # model class, val clips, ranks, val on GPU
+    train_split._need_gpu("fit")
+    if not next(net.parameters()).is_cuda:
+        raise RuntimeError("fit: the network is on the CPU; the training step runs on the GPU only")
+    return recurrent, rank, world
+
+
+def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_points, lr=1e-3, decay_epochs=1, decay_rate=0.9,
+        seed=1234, mini_clip_len=5, vr_thres=0.3, out_dir=None, resume=None, on_epoch=None, rank=0, world=1, group=None, args=None):
+    """The reference's ``train()`` (main.py:104-170) on two device-resident splits, without its plots and log files; the defaults
+    are configs.yaml's.  One TrainStep (Adam, weight decay 1e-4) and one StepLR (``make_schedule``), then per epoch:
+
+      1. train: ``train_epoch`` (CMFlow, RaFlow) or ``train_epoch_clips`` (CMFlow_T) on ``train_split``, batches keyed by
+         (seed, epoch, step);
+      2. validate: ``evaluate.eval_epoch`` / ``eval_epoch_clips`` on ``val_split`` at ``val_batch_size`` with seed ``seed + 1`` (its
+         draws come from another Philox stream than the training draws); the score is ``sf_metric['rne']``;
+      3. keep the best: ``replaces_best`` (the reference's ``>=``: a tie replaces, NaN never does); rank 0 then writes
+         ``out_dir/models/model.best.t7`` -- ``net.state_dict()`` and nothing else, the reference's file, which its model loads;
+      4. ``scheduler.step()``;
+      5. rank 0 writes the resume point ``out_dir/last.pt``: model, optimizer (both Adam moment arrays and the step count) and
+         scheduler state, the next epoch, ``best``, the histories, ``net.training`` as the validation left it, and the settings.
+         Both files are written under a temporary name and renamed;
+      6. ``on_epoch(epoch, record)``: the place of the reference's log lines; ``record`` holds the epoch's ``lr``, ``train_loss``,
+         ``loss_items``, ``val_score``, ``best`` and ``is_best``.
+
+    -> the history: ``train_loss``, ``loss_items`` (one dict per epoch), ``val_score``, ``lr`` (the rate each epoch trained with), one
+    entry per epoch, and ``best``.  The host reads the device once per epoch -- one small vector with the score and the epoch's
+    training statistics -- and never inside an epoch.
+
+    BatchNorm regime.  ``fit`` never calls ``net.train()`` for CMFlow / RaFlow, because the reference does not (train_one_epoch,
+    main_util.py:39-90): pass a fresh network in train mode and epoch 0 trains under train-mode BatchNorm, the first validation's
+    ``net.eval()`` (main_util.py:96) sticks, and every later epoch trains under eval-mode BatchNorm (running statistics, gradients
+    still flowing).  CMFlow_T stays in train mode in every training epoch: train_one_epoch_seq calls ``net.train()`` itself
+    (clip_util.py:25).  Pass a network in eval mode and all epochs run under eval-mode BatchNorm.
+
+    ``resume=path`` (a ``last.pt``): restores everything listed under 5, ``net.training`` included, and continues at the stored
+    epoch; the batches depend on (seed, epoch, step) only, so the continued run is bit for bit the uninterrupted one.  Stored
+    settings (model class, batch sizes, num_points, seed, lr, schedule, mini_clip_len, vr_thres, world, the splits' frame
+    counts) that differ from the call's raise ValueError -- ``epochs`` may differ, that is how a run is extended.
+
+    Data parallel: ``rank`` / ``world`` / ``group`` go to the iterators (``batch_size`` and ``val_batch_size`` are per rank), to the
+    TrainStep's gradient all-reduce and to the validation.  The score is all-reduced inside the validation, so every rank takes the
+    same decisions; the epoch's training statistics are averaged over the ranks in one all-reduce per epoch, so every rank returns
+    the same history.  BatchNorm's running statistics are per rank during an epoch (as nn.DataParallel's are per replica); before
+    every validation rank 0's are broadcast, so all ranks validate and continue with the network rank 0 saves.  Only rank 0 writes files; a resumed run reads the one ``last.pt`` on every rank.  Start the ranks from
+    identical parameters (``dp.broadcast_module``).
+
+    Refused before anything is launched and before any mode changes: ``epochs < 1``, CMFlow_T with a split without clip ranges, a
+    bad rank / world, ``world > 1`` without an initialised process group (ValueError); a model that is not CMFlow / CMFlow_T /
+    RaFlow (NotImplementedError); a split or a network that is not on the GPU (RuntimeError).
+    Whole-frame training (``epoch_ragged`` / ``step_ragged``) is not driven from here: its epoch 0 would need train-mode BatchNorm
+    on ragged batches, which raises by design.  The speed of a run is unmeasured."""
+    from . import evaluate as EV
+    recurrent, rank, world = _refuse(net, train_split, val_split, epochs, rank, world, group)
+    dev = train_split.device
+    settings = {"model": type(net).__name__, "batch_size": int(batch_size), "val_batch_size": int(val_batch_size),
+                "num_points": int(num_points), "seed": int(seed), "lr": float(lr), "decay_epochs": int(decay_epochs),
+                "decay_rate": float(decay_rate), "mini_clip_len": int(mini_clip_len), "vr_thres": float(vr_thres), "world": world,
+                "train_frames": len(train_split), "val_frames": len(val_split)}
+    state = None
+    if resume is not None:
+        state = torch.load(resume, map_location=dev)
+        if not isinstance(state, dict) or state.get("format") != "cmflow_amd.fit" or state.get("version") != RESUME_VERSION:
+            raise ValueError("fit: %s is not a resume point of format version %d" % (resume, RESUME_VERSION))
+        differ = {k: (state["settings"].get(k), v) for k, v in settings.items() if state["settings"].get(k) != v}
+        if differ:
+            raise ValueError("fit: the resume point was written by a run with other settings (stored, given): %s" % differ)
+    step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group)
+    scheduler = make_schedule(step.opt, decay_epochs, decay_rate)
+    history = {"train_loss": [], "loss_items": [], "val_score": [], "lr": [], "best": math.inf}     # main.py:110
+    first = 0
+    if state is not None:
+        net.load_state_dict(state["model"])
+        step.opt.load_state_dict(state["optimizer"])
+        scheduler.load_state_dict(state["scheduler"])
+        net.train(bool(state["training"]))
+        history, first = state["history"], int(state["epoch"])
+    writes = rank == 0 and out_dir is not None
+    if writes:
+        os.makedirs(os.path.join(out_dir, "models"), exist_ok=True)
+    for epoch in range(first, int(epochs)):
+        rate = step.opt.param_groups[0]["lr"]
+        if recurrent:
+            total, items = train_epoch_clips(step, train_split, batch_size, mini_clip_len, num_points, seed, epoch, rank, world)
+        else:
+            total, items = train_epoch(step, train_split, batch_size, num_points, seed, epoch, rank, world)
+        if world > 1:
+            _broadcast_buffers(net, group)
+        if recurrent:
+            sf = EV.eval_epoch_clips(net, val_split, val_batch_size, mini_clip_len, num_points, seed + 1, epoch, args,
+                                     rank=rank, world=world, group=group)[0]
+        else:
+            sf = EV.eval_epoch(net, val_split, val_batch_size, num_points, seed + 1, epoch, args, rank=rank, world=world,
+                               group=group)[0]
+        stats = torch.stack([total, *items.values()])
+        if world > 1:                                               # this rank's statistics -> the mean over the ranks
+            dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
+            stats = stats / world
+        numbers = torch.cat((sf["rne"].reshape(1), stats)).tolist()             # the epoch's one read of the device
+        score, train_loss = numbers[0], numbers[1]
+        history["lr"].append(rate)
+        history["train_loss"].append(train_loss)
+        history["loss_items"].append(dict(zip(items, numbers[2:])))
+        history["val_score"].append(score)
+        is_best = replaces_best(history["best"], score)
+        if is_best:
+            history["best"] = score
+            if writes:
+                save_atomic(net.state_dict(), os.path.join(out_dir, BEST_FILE))
+        scheduler.step()
+        if writes:
+            save_atomic({"format": "cmflow_amd.fit", "version": RESUME_VERSION, "settings": settings, "epoch": epoch + 1,
+                         "model": net.state_dict(), "optimizer": step.opt.state_dict(), "scheduler": scheduler.state_dict(),
+                         "training": bool(net.training), "history": history}, os.path.join(out_dir, LAST_FILE))
+        if on_epoch is not None:
+            on_epoch(epoch, {"lr": rate, "train_loss": train_loss, "loss_items": history["loss_items"][-1], "val_score": score,
+                             "best": history["best"], "is_best": is_best})
+    return history
