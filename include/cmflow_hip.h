@@ -811,6 +811,56 @@ int cmf_draw_frames(int B, int nmax1, int nmax2, int nframes, const float *tab1,
                     float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
                     float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *n1, int *n2, void *stream);
 
+/* ---- from raw radar scans to the packed split (cmflow_amd/prepare.py) ----------------------------------------
+ * The arithmetic of the reference's offline preprocess step (preprocess/utils/get_flow_samples.py) on batches of scans and pairs.
+ * Scans are packed: scans (scan_off[nscans], ncols >= 5) float32 rows x y z RCS v_r ..., scan_off (nscans + 1) int32 row offsets.
+ * Calibration: t_camera_radar (16 doubles, row-major 4 x 4) and projection (12 doubles, row-major 3 x 4), one set for all scans
+ * (calib_per_scan = 0) or one per scan (calib_per_scan = 1: (nscans,16), (nscans,12)).
+ * The input filter on a row: p_cam = t_camera_radar [x y z 1], uvw = projection p_cam, u = rint(uvw0 / uvw2), v = rint(uvw1 / uvw2)
+ * (half to even), all in float64; kept when 0 < u <= width, 0 < v <= height and zlo <= z <= zhi.  There is no depth test: a point
+ * behind the camera whose projection lands in the image is kept, as in the reference.  A row whose uvw2 is zero or not finite is
+ * dropped (the reference's result is undefined there).  Kept rows keep scan order.
+ *
+ * cmf_prepare_count: the filter on every row, one workgroup per scan, any scan length.
+ *   -> keep (rows) int32: the row's position among the kept rows of its scan, or -1 for a dropped row; uv (rows,2) int32: the pixel
+ *   of a kept row (0, 0 for a dropped one); count (nscans) int32: kept rows per scan. */
+int cmf_prepare_count(int nscans, int ncols, const float *scans, const int *scan_off, const double *t_camera_radar,
+                      const double *projection, int calib_per_scan, int width, int height, double zlo, double zhi,
+                      int *keep, int *uv, int *count, void *stream);
+
+/* cmf_prepare_scans: the inference front end -- the same filter, the kept rows of scan s written in scan order to
+ *   pc (nscans,3,nmax) = x y z and ft (nscans,3,nmax) = v_r RCS RCS, CMFlow.forward_ragged's padded layout; n (nscans) int32 =
+ *   min(kept, nmax) (a scan with more kept rows than nmax is truncated); slots from n on are exact zeros.  nmax <=
+ *   CMF_DRAW_MAX_NPOINTS. */
+int cmf_prepare_scans(int nscans, int ncols, int nmax, const float *scans, const int *scan_off, const double *t_camera_radar,
+                      const double *projection, int calib_per_scan, int width, int height, double zlo, double zhi,
+                      float *pc, float *ft, int *n, void *stream);
+
+/* cmf_prepare_pairs: the tab1 / tab2 rows (cmf_draw_batch's layout) of npairs frame pairs, one workgroup per pair.
+ *   keep, uv: cmf_prepare_count's results for the same scans.  pairs (npairs,2) int32: scan of frame 1, scan of frame 2.  off1, off2
+ *   (npairs + 1) int32: the pair's first row in tab1 / tab2 -- the prefix sums of count[pairs[:,0]] / count[pairs[:,1]], which the
+ *   host forms; a pair with more than CMF_DRAW_MAX_POINTS kept rows in a cloud is the caller's error (its points beyond that number
+ *   stay background).  t_inv (npairs,16) doubles: inv(radar1_radar2), the frame-1 -> frame-2 rigid transform of static points.
+ *   boxes (box_off[npairs], CMF_PREP_BOX_DOUBLES) doubles, box_off (npairs + 1) int32: the matched boxes of every pair, a record =
+ *   centre 3 | rotation 9 (row-major; columns = box axes) | half extents 3 | T_b1_b2 16 (row-major) | score.  boxes must not be NULL
+ *   (pass one unused record when there is none).
+ *   Foreground: boxes in record order; a point is in a box when |(p - c) . axis_a| <= half_a for a = 0, 1, 2 (closed); its in-box
+ *   flow is (T_b1_b2 [p 1])[:3] - p.  A box that holds at least one point and whose largest in-box flow norm is < 3 gives its points
+ *   that flow (rounded to float32), confidence (float)score, and makes them foreground; a later box overwrites an earlier one.
+ *   mode CMF_PREP_MODE_GT: flow_r = (t_inv [p 1])[:3] - p; a foreground point with ||label - flow_r|| > 0.05 (the float32 label, in
+ *   float64) keeps its label with mask = 1 - confidence (float32); every other point gets label (float)flow_r, mask 1; u, v and
+ *   optical flow are zeros.  mode CMF_PREP_MODE_PSEUDO: foreground as above without the 0.05 rule, background label 0 mask 1;
+ *   u, v = the filter's pixel; optical flow = flow[pair][v - 1][u - 1][0..1] from a (height,width,2) float32 image, zeros when
+ *   flow or flow[pair] is NULL (flow: npairs device pointers in device memory).
+ *   -> tab1 (off1[npairs],14), tab2 (off2[npairs],6). */
+#define CMF_PREP_BOX_DOUBLES 32
+#define CMF_PREP_MODE_GT 0
+#define CMF_PREP_MODE_PSEUDO 1
+int cmf_prepare_pairs(int npairs, int ncols, const float *scans, const int *scan_off, const int *keep, const int *uv,
+                      const int *pairs, const int *off1, const int *off2, const double *t_inv, const double *boxes,
+                      const int *box_off, int mode, const float *const *flow, int width, int height,
+                      float *tab1, float *tab2, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
