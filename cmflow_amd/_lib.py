@@ -87,6 +87,11 @@ SIGNATURES = {
     "cmf_colsum_finalize": [_ci, _ci, _vp, _vp, _vp, _vp, _vp],
     "cmf_group_affine": [_ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp],
     "cmf_adam_step": [_ci, _vp, _vp, _ll, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _ll, _vp],
+    "cmf_grad_norm_parts": [_ll],
+    "cmf_grad_sumsq": [_ll, _vp, _vp, _vp],
+    "cmf_grad_norm": [_ll, _vp, _vp, _vp, _vp],
+    "cmf_adam_step_guarded": [_ci, _vp, _vp, _ll, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _ll,
+                              ctypes.c_double, _ci, _vp, _vp, _vp],
     "cmf_group_prep": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp],
     "cmf_gemm_gather_affine": [_ci, _ci, _ci, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp],
     "cmf_gemm_dx_gather": [_ci, _ci, _ci, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -10,6 +10,8 @@ single ``all_reduce(SUM)`` per optimizer step and scaled by 1/world.  Nothing is
 the forward pass.  Parameters that never receive a gradient (the 12 unused WeightNet-BN
 tensors) stay outside the bucket with grad=None, so Adam skips them as it does in the reference.
 """
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -71,14 +73,52 @@ class FlatGradBucket:
         return lo, hi - lo
 
 
+def guard_options(max_grad_norm=None, skip_nonfinite=False):
+    """The two options of the guarded optimizer step, checked: -> (max_grad_norm as a float or None, skip_nonfinite as a bool).
+    ``max_grad_norm`` is a positive finite number or None (no clipping); 0, a negative number, NaN and inf raise ValueError -- a
+    clip that can never act, or that zeroes every step, is a mistake and not a setting."""
+    if max_grad_norm is not None:
+        if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)):
+            raise ValueError("max_grad_norm must be a positive finite number or None, not %r" % (max_grad_norm,))
+        max_grad_norm = float(max_grad_norm)
+        if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+            raise ValueError("max_grad_norm must be a positive finite number or None, not %r" % (max_grad_norm,))
+    return max_grad_norm, bool(skip_nonfinite)
+
+
+def grad_norm(bucket):
+    """The L2 norm of the bucket's gradient as a 0-d float64 device tensor: cmf_grad_norm, two launches on the current stream, no
+    host read.  The sum of squares is accumulated in double over a partition that depends on the bucket's size alone, in a fixed
+    order (relative error <= numel * 2^-53, bit-reproducible); a NaN or +-Inf gradient gives a non-finite norm.  The value a
+    guarded FlatAdam step on the same bucket decides by is ``float32(grad_norm(bucket))``."""
+    from . import _lib
+    flat = bucket.flat
+    parts = _lib.lib().cmf_grad_norm_parts(bucket.numel)
+    partials = torch.empty(parts, dtype=torch.float64, device=flat.device)
+    out = torch.empty(2, dtype=torch.float64, device=flat.device)
+    _lib.check(_lib.lib().cmf_grad_norm(bucket.numel, _lib.dev_ptr(flat, torch.float32), partials.data_ptr(), out.data_ptr(),
+                                        _lib.stream_ptr()), "cmf_grad_norm")
+    return out[1]
+
+
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam (L2 weight decay, no amsgrad: the reference's optimizer, main.py:107) over a FlatGradBucket as ONE kernel
     launch (cmf_adam_step): the gradients already lie contiguously in the bucket, the moments are two flat arrays in the same order, and
     the parameters stay where the module holds them (a device table of their addresses).  torch's fused Adam needs six multi-tensor
     launches for the model's 182 tensors at the very end of a step.  A torch Optimizer all the same: lr schedulers act on
-    param_groups[0]['lr'] (the reference steps a StepLR per epoch, main.py:108,151)."""
+    param_groups[0]['lr'] (the reference steps a StepLR per epoch, main.py:108,151).
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    The guard (off by default: ``step()`` is then the one cmf_adam_step launch).  ``max_grad_norm`` clips by the L2 norm of the whole
+    bucket with torch's ``clip_grad_norm_`` formula, ``skip_nonfinite`` leaves parameters and both moment arrays untouched when that
+    norm is NaN or Inf.  With either on, ``step()`` is cmf_grad_sumsq followed by cmf_adam_step_guarded (include/cmflow_hip.h has the
+    formula): the decision is taken on the device, the host reads nothing.  The bucket itself is NOT scaled -- it is zeroed before
+    the next backward anyway -- so ``p.grad`` read after a clipped step holds the unclipped gradient.  ``steps`` counts calls: a
+    skipped call advances the bias corrections like any other.  ``record`` (8 float64 on the device, see ``guard_stats``) counts
+    what the guard did.  Not guarded: BatchNorm's running statistics, which a train-mode forward has already updated."""
+
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+        self.max_grad_norm, self.skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         super().__init__(bucket.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise ValueError("FlatAdam: one parameter group (the bucket's parameters) -- per-group options are not supported")
@@ -88,6 +128,22 @@ class FlatAdam(torch.optim.Optimizer):
         self.steps = 0
         self._ptrs = None
         self._tables()
+        if self.guarded:
+            from . import _lib
+            parts = _lib.lib().cmf_grad_norm_parts(bucket.numel)
+            self._partials = torch.zeros(parts, dtype=torch.float64, device=bucket.flat.device)
+            self.record = torch.zeros(8, dtype=torch.float64, device=bucket.flat.device)
+
+    def guard_stats(self, reset=False):
+        """A copy of the guard's record, a float64 device tensor (no host read): [0] step() calls, [1] calls with a non-finite norm,
+        [2] clipped calls, [3] the sum and [4] the maximum of the float32 norm over the finite calls, [5] the last sum of squares,
+        [6] the last norm, [7] the last scale.  ``reset=True`` zeroes the record on the device behind the copy."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdam.guard_stats: the guard is off (max_grad_norm=None, skip_nonfinite=False)")
+        out = self.record.clone()
+        if reset:
+            self.record.zero_()
+        return out
 
     def _tables(self):
         ps = self.bucket.params
@@ -120,10 +176,18 @@ class FlatAdam(torch.optim.Optimizer):
             raise RuntimeError("FlatAdam: add_param_group is not supported (one group: the bucket's parameters)")
         g = self.param_groups[0]
         self.steps += 1
-        _lib.check(_lib.lib().cmf_adam_step(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, b.flat.data_ptr(),
-                                            self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), float(g["lr"]), float(g["betas"][0]),
-                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.steps,
-                                            _lib.stream_ptr()), "cmf_adam_step")
+        hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.steps)
+        if self.guarded:
+            stream = _lib.stream_ptr()
+            _lib.check(_lib.lib().cmf_grad_sumsq(b.numel, b.flat.data_ptr(), self._partials.data_ptr(), stream), "cmf_grad_sumsq")
+            _lib.check(_lib.lib().cmf_adam_step_guarded(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel,
+                                                        b.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *hyper,
+                                                        self.max_grad_norm or 0.0, int(self.skip_nonfinite), self._partials.data_ptr(),
+                                                        self.record.data_ptr(), stream), "cmf_adam_step_guarded")
+        else:
+            _lib.check(_lib.lib().cmf_adam_step(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, b.flat.data_ptr(),
+                                                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *hyper, _lib.stream_ptr()),
+                       "cmf_adam_step")
         # the kernel writes the parameters through raw pointers: bump their autograd version counters like an in-place torch op would,
         # so that a backward pass through a graph recorded BEFORE this step raises instead of silently using the updated weights
         bump = getattr(torch.autograd.graph, "increment_version", None)
@@ -137,6 +201,8 @@ class FlatAdam(torch.optim.Optimizer):
     def state_dict(self):
         d = super().state_dict()
         d["flat"] = dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, steps=self.steps)
+        if self.guarded:
+            d["flat"]["guard"] = self.record
         return d
 
     def load_state_dict(self, d):
@@ -145,7 +211,8 @@ class FlatAdam(torch.optim.Optimizer):
         the module's parameters (the reference's `torch.optim.Adam(net.parameters())`, main.py:107, or an oracle / CPU run): its
         indices are then positions in module.parameters(); the parameters outside the bucket (never used, frozen) have no state in
         such a checkpoint either and are skipped.  The moments are scattered into the flat arrays.  Anything else raises:
-        restarting the moments silently would change the training run."""
+        restarting the moments silently would change the training run.  A guarded optimizer restores its record from
+        ``flat["guard"]`` and zeroes it for a checkpoint without one (the counters are diagnostics, not state of the run)."""
         d = dict(d)
         flat = d.pop("flat", None)
         per_param = d.get("state") or {}
@@ -168,6 +235,10 @@ class FlatAdam(torch.optim.Optimizer):
         super().load_state_dict(dict(d, state={}, param_groups=[group]))
         if flat is not None:
             self.exp_avg.copy_(flat["exp_avg"]); self.exp_avg_sq.copy_(flat["exp_avg_sq"]); self.steps = int(flat["steps"])
+            if self.guarded and "guard" in flat:
+                self.record.copy_(flat["guard"])
+            elif self.guarded:
+                self.record.zero_()
             return
         if not per_param:
             return                                           # a fresh optimizer's checkpoint: nothing to restore

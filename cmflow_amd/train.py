@@ -18,13 +18,19 @@ import torch
 import torch.distributed as dist
 
 from . import synth
-from .dp import FlatAdam, FlatGradBucket, SegmentedReducer
+from .dp import FlatAdam, FlatGradBucket, SegmentedReducer, guard_options
 from .fused_blocks import join_side_streams
 from .losses import RadarFlowLoss, make_labels, make_labels_ragged
 
 
 class TrainStep:
-    def __init__(self, net, vr_thres=0.3, lr=0.001, weight_decay=1e-4, camera_projection=None, t_camera_radar=None, group=None):
+    def __init__(self, net, vr_thres=0.3, lr=0.001, weight_decay=1e-4, camera_projection=None, t_camera_radar=None, group=None,
+                 max_grad_norm=None, skip_nonfinite=False):
+        """``max_grad_norm`` / ``skip_nonfinite``: the guard of the optimizer step (dp.FlatAdam) -- clip by the L2 norm of the whole
+        gradient, leave parameters and moments untouched when that norm is not finite.  It runs inside ``opt.step()``, behind the
+        all-reduce, so every rank sees the same bucket and takes the same decision without a further collective.  On a CPU model a
+        requested guard raises ValueError: torch's Adam has none and nothing here falls back."""
+        max_grad_norm, skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
         self.net = net
         self.group = group                                         # the process group of the gradient all-reduce (None: the default one)
         dev = next(net.parameters()).device
@@ -34,8 +40,10 @@ class TrainStep:
         self.bucket = FlatGradBucket(net)
         # the reference's Adam (main.py:107) as one launch over the flat bucket (dp.FlatAdam; torch's fused Adam: six launches at the
         # tail of the step); on a CPU model torch's own
-        self.opt = (FlatAdam(self.bucket, lr=lr, weight_decay=weight_decay) if dev.type == "cuda"
-                    else torch.optim.Adam(self.bucket.params, lr=lr, weight_decay=weight_decay))
+        if dev.type != "cuda" and (max_grad_norm is not None or skip_nonfinite):
+            raise ValueError("TrainStep: max_grad_norm / skip_nonfinite need the GPU optimizer (dp.FlatAdam); the model is on the CPU")
+        self.opt = (FlatAdam(self.bucket, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                    if dev.type == "cuda" else torch.optim.Adam(self.bucket.params, lr=lr, weight_decay=weight_decay))
         self.recurrent = hasattr(net, "gru")
         self.self_supervised = hasattr(net, "fd_layer")
         # the scales of an encoder run on side streams while the gradient bucket lives on the main stream
@@ -220,6 +228,7 @@ def train_epoch_clips(step, split, batch_size, mini_clip_len, npoints, seed, epo
 BEST_FILE = os.path.join("models", "model.best.t7")               # main.py:147-149, under out_dir
 LAST_FILE = "last.pt"
 RESUME_VERSION = 1
+GUARD_KEYS = ("grad_norm_mean", "grad_norm_max", "clipped_steps", "skipped_steps")      # history / on_epoch entries of a guarded fit
 
 
 def make_schedule(opt, decay_epochs, decay_rate):
@@ -269,7 +278,8 @@ def _refuse(net, train_split, val_split, epochs, rank, world, group):
 
 
 def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_points, lr=1e-3, decay_epochs=1, decay_rate=0.9,
-        seed=1234, mini_clip_len=5, vr_thres=0.3, out_dir=None, resume=None, on_epoch=None, rank=0, world=1, group=None, args=None):
+        seed=1234, mini_clip_len=5, vr_thres=0.3, out_dir=None, resume=None, on_epoch=None, rank=0, world=1, group=None, args=None,
+        max_grad_norm=None, skip_nonfinite=False):
     """The reference's ``train()`` (main.py:104-170) on two device-resident splits, without its plots and log files; the defaults
     are configs.yaml's.  One TrainStep (Adam, weight decay 1e-4) and one StepLR (``make_schedule``), then per epoch:
 
@@ -308,29 +318,46 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     every validation rank 0's are broadcast, so all ranks validate and continue with the network rank 0 saves.  Only rank 0 writes files; a resumed run reads the one ``last.pt`` on every rank.  Start the ranks from
     identical parameters (``dp.broadcast_module``).
 
-    Refused before anything is launched and before any mode changes: ``epochs < 1``, CMFlow_T with a split without clip ranges, a
+    Guard.  ``max_grad_norm`` / ``skip_nonfinite`` go to the TrainStep (dp.FlatAdam: clip by the gradient's L2 norm; skip a step whose
+    norm is NaN or Inf, so that one bad batch does not put NaN into the Adam moments for good).  With either on, the epoch's one read
+    also carries the optimizer's ``guard_stats(reset=True)``, and the history and the ``on_epoch`` record gain ``grad_norm_mean`` (over
+    the epoch's steps with a finite norm; NaN if there was none), ``grad_norm_max``, ``clipped_steps`` and ``skipped_steps`` (0 unless
+    ``skip_nonfinite``).  They are not averaged over the ranks: the guard reads the all-reduced bucket, so they are identical on
+    all of them.  The settings hold the two options only when a guard is on, and a resume point without them compares as "off";
+    with the guard off, history, record and ``last.pt`` have exactly the keys they had without it.  The guard protects parameters
+    and moments; train-mode BatchNorm updates its running statistics in the forward, so a non-finite INPUT still reaches those.
+
+    Refused before anything is launched and before any mode changes: a bad ``max_grad_norm`` (ValueError), ``epochs < 1``, CMFlow_T with a split without clip ranges, a
     bad rank / world, ``world > 1`` without an initialised process group (ValueError); a model that is not CMFlow / CMFlow_T /
     RaFlow (NotImplementedError); a split or a network that is not on the GPU (RuntimeError).
     Whole-frame training (``epoch_ragged`` / ``step_ragged``) is not driven from here: its epoch 0 would need train-mode BatchNorm
     on ragged batches, which raises by design.  The speed of a run is unmeasured."""
     from . import evaluate as EV
+    max_grad_norm, skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
+    guarded = max_grad_norm is not None or skip_nonfinite
     recurrent, rank, world = _refuse(net, train_split, val_split, epochs, rank, world, group)
     dev = train_split.device
     settings = {"model": type(net).__name__, "batch_size": int(batch_size), "val_batch_size": int(val_batch_size),
                 "num_points": int(num_points), "seed": int(seed), "lr": float(lr), "decay_epochs": int(decay_epochs),
                 "decay_rate": float(decay_rate), "mini_clip_len": int(mini_clip_len), "vr_thres": float(vr_thres), "world": world,
                 "train_frames": len(train_split), "val_frames": len(val_split)}
+    if guarded:
+        settings.update(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     state = None
     if resume is not None:
         state = torch.load(resume, map_location=dev)
         if not isinstance(state, dict) or state.get("format") != "cmflow_amd.fit" or state.get("version") != RESUME_VERSION:
             raise ValueError("fit: %s is not a resume point of format version %d" % (resume, RESUME_VERSION))
-        differ = {k: (state["settings"].get(k), v) for k, v in settings.items() if state["settings"].get(k) != v}
+        off = {"max_grad_norm": None, "skip_nonfinite": False}                       # a resume point without them: guard off
+        stored, given = dict(off, **state["settings"]), dict(off, **settings)
+        differ = {k: (stored.get(k), v) for k, v in given.items() if stored.get(k) != v}
         if differ:
             raise ValueError("fit: the resume point was written by a run with other settings (stored, given): %s" % differ)
-    step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group)
+    step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     scheduler = make_schedule(step.opt, decay_epochs, decay_rate)
     history = {"train_loss": [], "loss_items": [], "val_score": [], "lr": [], "best": math.inf}     # main.py:110
+    if guarded:
+        history.update({k: [] for k in GUARD_KEYS})
     first = 0
     if state is not None:
         net.load_state_dict(state["model"])
@@ -359,8 +386,18 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
         if world > 1:                                               # this rank's statistics -> the mean over the ranks
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
             stats = stats / world
-        numbers = torch.cat((sf["rne"].reshape(1), stats)).tolist()             # the epoch's one read of the device
+        parts = (sf["rne"].reshape(1), stats) + ((step.opt.guard_stats(reset=True),) if guarded else ())
+        numbers = torch.cat(parts).tolist()                                     # the epoch's one read of the device
         score, train_loss = numbers[0], numbers[1]
+        guard = {}
+        if guarded:                                                 # identical on every rank: the guard reads the reduced bucket
+            record = numbers[-8:]
+            numbers = numbers[:-8]
+            finite = record[0] - record[1]
+            guard = {"grad_norm_mean": record[3] / finite if finite > 0 else math.nan, "grad_norm_max": record[4],
+                     "clipped_steps": int(record[2]), "skipped_steps": int(record[1]) if skip_nonfinite else 0}
+            for k in GUARD_KEYS:
+                history[k].append(guard[k])
         history["lr"].append(rate)
         history["train_loss"].append(train_loss)
         history["loss_items"].append(dict(zip(items, numbers[2:])))
@@ -377,5 +414,5 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
                          "training": bool(net.training), "history": history}, os.path.join(out_dir, LAST_FILE))
         if on_epoch is not None:
             on_epoch(epoch, {"lr": rate, "train_loss": train_loss, "loss_items": history["loss_items"][-1], "val_score": score,
-                             "best": history["best"], "is_best": is_best})
+                             "best": history["best"], "is_best": is_best, **guard})
     return history

@@ -478,6 +478,43 @@ int cmf_setconv_path(const cmf_setconv_desc *d);
 int cmf_adam_step(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m, float *v,
                   double lr, double beta1, double beta2, double eps, double weight_decay, long long step, void *stream);
 
+/* The guarded optimizer step: the L2 norm of the flat gradient bucket on the device, clipping by it, and skipping a step whose norm is
+ * not finite -- two launches behind the backward pass, no host read, bit-reproducible.
+ *
+ * cmf_grad_norm_parts(total): the number P of workgroups (1 <= P <= 256; 0 for total <= 0) of the sum of squares and the length of
+ * `partials`.  Host arithmetic on `total` alone (not the device, its CU count or the environment), callable without a device:
+ * slabs = ceil(total / 1024), P = min(256, ceil(slabs / 4)); workgroup b owns the contiguous slabs [b slabs / P, (b + 1) slabs / P).
+ * cmf_grad_sumsq: partials[b] = the sum over workgroup b's elements of (double)x * (double)x, accumulated in double (the square of an
+ * fp32 value is exact in double, only the additions round: relative error <= total * 2^-53), lanes, waves and LDS folded in a fixed
+ * order, no atomics.  A NaN or +-Inf element makes its partial non-finite; finite fp32 values cannot overflow.  `grad` must be 16-byte
+ * aligned (hipErrorInvalidValue otherwise).
+ * cmf_grad_norm: cmf_grad_sumsq, then one workgroup folds the P partials in a fixed order: out[0] = sumsq, out[1] = sqrt(sumsq), doubles.
+ *
+ * cmf_adam_step_guarded: cmf_adam_step behind a prologue.  `partials` is what cmf_grad_sumsq left for the same `grad`; every
+ * workgroup folds it with the fold cmf_grad_norm uses (the same bits) and derives, identically everywhere:
+ *     normf     = (float)sqrt(sumsq)                 // double sqrt, rounded once
+ *     nonfinite = !isfinite(sumsq)
+ *     if (nonfinite && skip)  -> return before any store to p, m, v
+ *     scale = 1.f
+ *     if (!nonfinite && clip_on) { coef = max_norm_f / (normf + 1e-6f); scale = coef < 1.f ? coef : 1.f; }   // torch's clip_grad_norm_ formula, in fp32
+ *     g = fmaf(wd, p, grad[e] * scale)               // then exactly cmf_adam_step's update
+ * clip_on = max_grad_norm is positive and finite (<= 0 or +inf: no clipping; NaN: hipErrorInvalidValue), max_norm_f = (float)max_grad_norm.
+ * `grad` is NOT modified: read after the step it holds the unclipped gradient.  A non-finite norm with skip_nonfinite = 0 means
+ * "guard off": scale = 1 and the update is cmf_adam_step's, NaNs included.  With scale = 1 and no skip the result is bit-identical to
+ * cmf_adam_step's.
+ * step: as in cmf_adam_step the bias corrections are formed on the host, in double, from `step` -- so `step` counts CALLS, and a skipped
+ * call advances it like any other (no device-side pow, and the guarded step equals the unguarded one whenever nothing is clipped or
+ * skipped).
+ * record: 8 doubles in device memory, updated by one lane with plain loads and stores (launches on one stream are ordered):
+ *   [0] calls   [1] calls with a non-finite norm   [2] clipped calls (scale < 1)   [3] sum of normf over the finite calls
+ *   [4] max of normf over the finite calls   [5] last sumsq   [6] last normf   [7] last scale */
+int cmf_grad_norm_parts(long long total);
+int cmf_grad_sumsq(long long total, const float *grad, double *partials, void *stream);
+int cmf_grad_norm(long long total, const float *grad, double *partials, double *out, void *stream);
+int cmf_adam_step_guarded(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
+                          float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
+                          double max_grad_norm, int skip_nonfinite, const double *partials, double *record, void *stream);
+
 /* Float offsets, inside `saved`, of the six per-layer BatchNorm blocks (mean | invstd | a | c, 4*C_l floats each). */
 int cmf_setconv_bn_offsets(const cmf_setconv_desc *d, long long *offsets6);
 
