@@ -149,6 +149,10 @@ SIGNATURES = {
     "cmf_prepare_count": [_ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "cmf_prepare_scans": [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "cmf_prepare_pairs": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp],
+    # a test run's per-frame results (results.py)
+    "cmf_pack_results": [_ci, _ci, _ci, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_eval_metrics_frames": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _vp, _vp, _vp, _vp],
+    "cmf_pose_chain": [_ci, _ci, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

@@ -175,6 +175,39 @@ __global__ __launch_bounds__(64) void eval_finalize_counted_kernel(int b, int ld
     metrics[t] = acc / (double)b;
 }
 
+// Per-frame results (cmf_eval_metrics_frames, cmflow_amd/results.py): eval_finalize_counted_kernel's per-sample value v of metric t,
+// the same expressions in the same order, written to row frames[i] of a (F,14) table instead of being averaged.  One workgroup
+// per sample; frame ids are clamped to [0, F-1].
+__global__ __launch_bounds__(64) void eval_finalize_frames_kernel(int ld, int nframes, const int *__restrict__ cnt, const int *__restrict__ frames,
+                                                                  const double *__restrict__ partial, double *__restrict__ table)
+{
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (t >= 14) return;
+    const double *s = partial + (size_t)i * EV_PART;
+    const double n = (double)max(0, min(cnt[i], ld));
+    const double mov = s[4] / (s[5] + 1e-6), stat = s[6] / s[7];              // np.mean of an empty selection is NaN
+    const double tp = s[10], tn = s[11], fp = s[12], fn = s[13];
+    double v;
+    switch (t) {
+    case 0: v = s[3] / n; break;
+    case 1: v = (mov + stat) / 2.0; break;
+    case 2: v = mov; break;
+    case 3: v = stat; break;
+    case 4: v = s[8] / n; break;
+    case 5: v = s[9] / n; break;
+    case 6: v = s[0] / n; break;
+    case 7: v = s[1] / n; break;
+    case 8: v = s[2] / n; break;
+    case 9: v = (tp + tn) / (((tp + tn) + fp) + fn); break;
+    case 10: v = 0.5 * (tp / (((tp + fp) + fn) + 1e-10) + tn / (((tn + fp) + fn) + 1e-10)); break;
+    case 11: v = tp / ((tp + fn) + 1e-10); break;
+    case 12: v = s[14]; break;
+    default: v = s[15]; break;
+    }
+    const int f = min(max(frames[i], 0), nframes - 1);
+    table[(size_t)f * 14 + t] = v;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Pseudo labels of the training step (main_util.py:63-67): dyn_mask = extract_dynamic_from_fg (:209-225) and the
 // motion-segmentation label mseg_label_RRV (:253-265), merged as where(dyn_mask == 1, mseg, dyn_mask).
@@ -300,5 +333,19 @@ extern "C" int cmf_eval_metrics_counted(int b, int n, const int *cnt, const floa
     hipLaunchKernelGGL(eval_sample_kernel<true>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
                        pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
     hipLaunchKernelGGL(eval_finalize_counted_kernel, dim3(1), dim3(64), 0, st, b, n, cnt, workspace, metrics);
+    return cmf_launch_status();
+}
+
+extern "C" int cmf_eval_metrics_frames(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
+                                       const float *pred_m, const float *gt_trans, const float *pred_trans,
+                                       float r_res, float theta_res, float phi_res, int nframes, const int *frames, double *table,
+                                       double *workspace, void *stream)
+{
+    CMF_CHECK_ARG(b > 0 && n > 0 && nframes > 0 && cnt && frames && table && workspace);
+    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(eval_sample_kernel<true>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
+                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    hipLaunchKernelGGL(eval_finalize_frames_kernel, dim3(b), dim3(64), 0, st, n, nframes, cnt, frames, workspace, table);
     return cmf_launch_status();
 }

@@ -12,6 +12,9 @@ frames, so the runs between two resets are independent: ``clip_test_resets`` res
 Data parallel (``rank``, ``world``, ``group``): every rank evaluates its share of the frames -- its slices of ``sweep``'s global
 batches, or the schedule groups ``g % world == rank`` -- and the sums, the frame count and the two transform arrays are all-reduced
 once each AFTER the loop, so every rank returns the result of the whole split.
+
+``test_split`` / ``test_split_clips`` are the same epochs with every frame's outputs and metrics kept on the device (results.py): the
+reference's ``--eval --save_res`` run.
 """
 import torch
 import torch.distributed as dist
@@ -191,6 +194,48 @@ def eval_split_clips(net, split, batch_size, update_len, args=None, on_batch=Non
     if world > 1:
         acc.all_reduce(group)
     return acc.result()
+
+
+# ---- test epochs that keep every frame's results (the reference's --eval --save_res run; results.py) ----------------------------------
+def _collecting(collector, on_batch):
+    if on_batch is None:
+        return collector
+
+    def both(batch, outputs):
+        collector(batch, outputs)
+        on_batch(batch, outputs)
+    return both
+
+
+def test_split(net, split, batch_size, args=None, sort_by_size=False, on_batch=None, rank=0, world=1, group=None):
+    """``eval_split`` that also keeps what the network predicted for every frame: a ``results.ResultCollector`` is its ``on_batch``
+    hook (a given ``on_batch`` is still called, after it), so flow, score, mask, both transforms and the 14 metrics of every frame
+    land in a ``results.SplitResults`` on the device without the loop ever waiting for it.  Arguments, refusals (``_check``, before
+    anything is allocated) and the epoch itself are eval_split's.  Data parallel: the store is all-reduced after eval_split's own
+    all-reduce (``SplitResults.all_reduce``), so every rank returns the whole split's.
+    -> (the five-tuple of eval_split, SplitResults)."""
+    from .results import ResultCollector
+    rank, world = _check(net, split, "test_split", False, rank, world, group)
+    collector = ResultCollector(split, args)
+    five = eval_split(net, split, batch_size, args, sort_by_size, _collecting(collector, on_batch), rank, world, group)
+    if world > 1:
+        collector.results.all_reduce(group)
+    return five, collector.results
+
+
+def test_split_clips(net, split, batch_size, update_len, args=None, on_batch=None, rank=0, world=1, group=None):
+    """``eval_split_clips`` (CMFlow-T's test protocol) with a ``results.ResultCollector`` as its hook, as ``test_split``.
+    -> (the five-tuple of eval_split_clips, SplitResults)."""
+    from .results import ResultCollector
+    rank, world = _check(net, split, "test_split_clips", True, rank, world, group)
+    collector = ResultCollector(split, args)
+    five = eval_split_clips(net, split, batch_size, update_len, args, _collecting(collector, on_batch), rank, world, group)
+    if world > 1:
+        collector.results.all_reduce(group)
+    return five, collector.results
+
+
+test_split.__test__ = test_split_clips.__test__ = False                 # entry points of the product, not tests
 
 
 # ---- validation epochs: frames resampled to num_points, in order (train()'s eval_one_epoch / eval_one_epoch_seq) -----------------------

@@ -898,6 +898,55 @@ int cmf_prepare_pairs(int npairs, int ncols, const float *scans, const int *scan
                       const int *box_off, int mode, const float *const *flow, int width, int height,
                       float *tab1, float *tab2, void *stream);
 
+/* ---- a test run's per-frame results kept on the device (cmflow_amd/results.py) ---------------------------------
+ * The store of a split of F frames is packed like its cloud-1 table: off1 (F+1) int32 as in cmf_draw_batch, and per point of cloud 1
+ * flow (off1[F],3), score (off1[F]) and mask8 (off1[F]) bytes; per frame trans_pred, trans_gt (F,16), done (F) bytes, metrics (F,14).
+ *
+ * cmf_pack_results: the outputs of one ragged batch (CMFlow.forward_ragged on a batch of cmf_draw_frames) into the store -- one
+ *   launch, the inverse of cmf_draw_frames.  frames, n1 (B) int32: the frame and the cloud-1 count of every slot, as cmf_draw_frames
+ *   wrote them; sf (B,3,nmax); stat_cls (B,nmax) or NULL (then score is not touched and may be NULL); mask (B,nmax) bytes;
+ *   pre_trans, gt_trans (B,16).  For slot s, f = frames[s] and rows i < min(n1[s], off1[f+1] - off1[f], nmax):
+ *     flow[off1[f] + i] = (sf[s,0,i], sf[s,1,i], sf[s,2,i]);  score[off1[f] + i] = stat_cls[s,i];  mask8[off1[f] + i] = mask[s,i];
+ *   and trans_pred[f] = pre_trans[s], trans_gt[f] = gt_trans[s], done[f] = 1.  Every value is a copy.
+ *   Guarantees: a packed row is written by exactly one thread per slot (no atomics); positions of a slot from that row count on -- the
+ *   padded part of the batch -- are never READ, so they may hold anything; a frame larger than nmax (a batch drawn with a too-small
+ *   nmax1) leaves its remaining rows unwritten.  The same frame in two slots of one call is allowed only in the sense that both slots
+ *   write it: with identical slot contents (the same frame through the same network) the two writes store identical values and the
+ *   result is defined; with different contents every row ends up with one slot's value or the other's, unspecified which.
+ *   Frame ids are clamped to [0, nframes-1] as in cmf_draw_frames; offsets are trusted to be ascending, and a frame whose rows would
+ *   not lie inside [0, total) (total = off1[nframes], passed on the host) has nothing written: a bad id or offset gives wrong data,
+ *   not an access outside the store.  B <= 65535, nmax <= CMF_DRAW_MAX_NPOINTS.
+ *
+ * cmf_eval_metrics_frames: cmf_eval_metrics_counted's per-sample metrics, scattered instead of averaged.  Arguments as there, plus
+ *   frames (b) int32 and table (nframes,14) doubles: row frames[s] (clamped to [0, nframes-1]) receives, for the 14 metrics in
+ *   cmf_eval_metrics' order, the per-sample value cmf_eval_metrics_counted averages -- the same kernel for the 16 partial sums and the
+ *   same expressions after it, so a row is, value for value (NaN for NaN), what cmf_eval_metrics_counted returns for that sample alone
+ *   at b = 1, and the mean of a batch's rows in slot order is what it returns for the batch.  No mean is taken and no other row of
+ *   the table is touched.  Two slots with the same frame write the same row; identical inputs give identical values.
+ *   workspace: 16 * b doubles.
+ *
+ * cmf_pose_chain: the sensor's pose along every clip from per-frame transforms -- a definition, not an approximation of one.
+ *   T (nframes,16) float32 row-major: T_k maps static points from scan-1 to scan-2 sensor coordinates of frame k.  clips (nclips,2)
+ *   int32 in DEVICE memory: [first, last) frame ranges, clamped to [0, nframes].  poses (nframes,16) float64.  Per clip [a, b):
+ *     P = I;  for k = a .. b-1:  P = P . inv(T_k);  poses[k] = P
+ *   with inv(T) = (R^T, -R^T t), the rigid inverse of odometry_util.se3_inverse, whether or not R is exactly orthonormal.
+ *   Arithmetic: float64 from the float32 entries; inv's translation is  -((R[0][r] t0 + R[1][r] t1) + R[2][r] t2);  an entry of
+ *   the product is  ((P[r][0] M[0][c] + P[r][1] M[1][c]) + P[r][2] M[2][c]) + P[r][3] M[3][c]  with M = inv(T_k) and its bottom row
+ *   (0,0,0,1) taking part as numbers; every multiplication and addition is rounded on its own (no contraction); the bottom row
+ *   of every pose is written as exactly (0,0,0,1).  tests/results_ref.py restates this in numpy, bit for bit.
+ *   One lane per clip walks its frames in order (a parallel scan would change the association).  Rows of poses outside every clip,
+ *   and an empty clip, are not written: the caller pre-fills poses (results.py: NaN).  Overlapping clips are the caller's error
+ *   (each writes its own chain; which one a shared row keeps is unspecified). */
+int cmf_pack_results(int B, int nmax, int nframes, const int *frames, const int *n1, const int *off1, long long total,
+                     const float *sf, const float *stat_cls, const unsigned char *mask, const float *pre_trans,
+                     const float *gt_trans, float *flow, float *score, unsigned char *mask8, float *trans_pred,
+                     float *trans_gt, unsigned char *done, void *stream);
+int cmf_eval_metrics_frames(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
+                            const float *pred_m, const float *gt_trans, const float *pred_trans,
+                            float r_res, float theta_res, float phi_res, int nframes, const int *frames, double *table,
+                            double *workspace, void *stream);
+int cmf_pose_chain(int nframes, int nclips, const float *T, const int *clips, double *poses, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
