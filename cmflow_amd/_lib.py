@@ -92,6 +92,11 @@ SIGNATURES = {
     "cmf_grad_norm": [_ll, _vp, _vp, _vp, _vp],
     "cmf_adam_step_guarded": [_ci, _vp, _vp, _ll, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _ll,
                               ctypes.c_double, _ci, _vp, _vp, _vp],
+    "cmf_adam_step_ema": [_ci, _vp, _vp, _ll, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _ll,
+                          _vp, ctypes.c_double, _vp],
+    "cmf_adam_step_guarded_ema": [_ci, _vp, _vp, _ll, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                  _ll, ctypes.c_double, _ci, _vp, _vp, _vp, ctypes.c_double, _vp],
+    "cmf_param_exchange": [_ci, _vp, _vp, _ll, _vp, _vp],
     "cmf_group_prep": [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp],
     "cmf_gemm_gather_affine": [_ci, _ci, _ci, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp],
     "cmf_gemm_dx_gather": [_ci, _ci, _ci, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -12,10 +12,15 @@
 constexpr int AD_THREADS = 256;
 constexpr int AD_CHUNK = 1024;                 // bucket elements per workgroup
 
+// EMA: the running average of the parameters rides in the same launch -- ema[e] += omd (pn - ema[e]) with pn the value just stored, one
+// explicit fmaf (no contraction choice), omd = (float)(1 - decay).  The lerp form's fixed point is pn itself: pn == ev gives ev back bit for
+// bit, where d ev + (1 - d) pn carries a relative bias of 2^-24 / (1 - d).  EMA = false is the kernel without it, expression for expression.
+template <bool EMA>
 __global__ __launch_bounds__(AD_THREADS) void adam_flat_kernel(int n_tensors, const long long *__restrict__ offsets /* [n + 1] */,
                                                                float *const *__restrict__ params, long long total,
                                                                const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v,
-                                                               float wd, float b1w, float b2, float b2w, float step_size, float bc2_sqrt, float eps)
+                                                               float wd, float b1w, float b2, float b2w, float step_size, float bc2_sqrt, float eps,
+                                                               float *__restrict__ ema, float omd)
 {
     const long long e0 = (long long)blockIdx.x * AD_CHUNK;
     // the tensor that holds the chunk's first element (binary search, one lane's worth of work), then a walk: most chunks lie in one tensor
@@ -38,20 +43,77 @@ __global__ __launch_bounds__(AD_THREADS) void adam_flat_kernel(int n_tensors, co
         const float vn = b2 * vv + b2w * (g * g);
         m[e] = mn; v[e] = vn;
         const float denom = sqrtf(vn) / bc2_sqrt + eps;
-        *p = pv - step_size * (mn / denom);
+        const float pn = pv - step_size * (mn / denom);
+        *p = pn;
+        if (EMA) { const float ev = ema[e]; ema[e] = fmaf(omd, pn - ev, ev); }
     }
 }
 
 // The hyper-parameters arrive as doubles (Python floats) and every derived scalar is formed in double before it is rounded to fp32
 // once, as torch does: 1 - beta is (float)(1.0 - beta), not 1.f - (float)beta (those differ by 1e-5 relative for beta2 = 0.999).
-extern "C" int cmf_adam_step(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
-                             float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step, void *stream)
+// ema == nullptr: the step without the average (ema_decay is not read).
+static int adam_launch(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m, float *v,
+                       double lr, double beta1, double beta2, double eps, double weight_decay, long long step, float *ema, double ema_decay,
+                       void *stream)
 {
     CMF_CHECK_ARG(n_tensors > 0 && offsets && params && total > 0 && grad && m && v && step >= 1 && lr >= 0.0);
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)cmf_divup(total, AD_CHUNK)), dim3(AD_THREADS), 0, (hipStream_t)stream, n_tensors, offsets,
+    const auto kernel = ema ? adam_flat_kernel<true> : adam_flat_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)cmf_divup(total, AD_CHUNK)), dim3(AD_THREADS), 0, (hipStream_t)stream, n_tensors, offsets,
                        params, total, grad, m, v, (float)weight_decay, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1),
-                       (float)sqrt(bc2), (float)eps);
+                       (float)sqrt(bc2), (float)eps, ema, ema ? (float)(1.0 - ema_decay) : 0.f);
+    return cmf_launch_status();
+}
+
+static int ema_check(const float *ema, double ema_decay)
+{
+    CMF_CHECK_ARG(ema && ((uintptr_t)ema & 3) == 0 && ema_decay > 0.0 && ema_decay < 1.0);      // a NaN decay fails both comparisons
+    return 0;
+}
+
+extern "C" int cmf_adam_step(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
+                             float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step, void *stream)
+{
+    return adam_launch(n_tensors, offsets, params, total, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.0, stream);
+}
+
+extern "C" int cmf_adam_step_ema(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
+                                 float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step, float *ema,
+                                 double ema_decay, void *stream)
+{
+    if (int err = ema_check(ema, ema_decay)) return err;
+    return adam_launch(n_tensors, offsets, params, total, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, ema, ema_decay, stream);
+}
+
+// Every parameter element swapped with flat[e], through the Adam kernel's address table and chunk walk: pure copies, so a second call
+// undoes the first bit for bit.
+__global__ __launch_bounds__(AD_THREADS) void param_exchange_kernel(int n_tensors, const long long *__restrict__ offsets /* [n + 1] */,
+                                                                    float *const *__restrict__ params, long long total,
+                                                                    float *__restrict__ flat)
+{
+    const long long e0 = (long long)blockIdx.x * AD_CHUNK;
+    int t = 0;
+    {
+        int lo = 0, hi = n_tensors;            // offsets[lo] <= e0 < offsets[hi]
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= e0) lo = mid; else hi = mid; }
+        t = lo;
+    }
+    for (int i = threadIdx.x; i < AD_CHUNK; i += AD_THREADS) {
+        const long long e = e0 + i;
+        if (e >= total) return;
+        int tt = t;
+        while (offsets[tt + 1] <= e) ++tt;
+        float *p = params[tt] + (e - offsets[tt]);
+        const float pv = *p, fv = flat[e];
+        *p = fv; flat[e] = pv;
+    }
+}
+
+extern "C" int cmf_param_exchange(int n_tensors, const long long *offsets, float *const *params, long long total, float *flat, void *stream)
+{
+    CMF_CHECK_ARG(n_tensors > 0 && offsets && params && total > 0 && flat && ((uintptr_t)flat & 3) == 0);
+    hipLaunchKernelGGL(param_exchange_kernel, dim3((unsigned)cmf_divup(total, AD_CHUNK)), dim3(AD_THREADS), 0, (hipStream_t)stream, n_tensors,
+                       offsets, params, total, flat);
     return cmf_launch_status();
 }
 
@@ -120,12 +182,14 @@ __global__ __launch_bounds__(AD_THREADS) void grad_norm_fold_kernel(const double
 
 // adam_flat_kernel behind a prologue: every workgroup folds the partials (2 KB, L2-resident) and derives the same decision.  The
 // update below is adam_flat_kernel's, expression for expression; with scale = 1 (grad[e] * 1.f is grad[e]) it gives the same bits.
+template <bool EMA>
 __global__ __launch_bounds__(AD_THREADS) void adam_flat_guarded_kernel(int n_tensors, const long long *__restrict__ offsets /* [n + 1] */,
                                                                        float *const *__restrict__ params, long long total,
                                                                        const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v,
                                                                        float wd, float b1w, float b2, float b2w, float step_size, float bc2_sqrt,
                                                                        float eps, const double *__restrict__ partials, int parts, int clip_on,
-                                                                       float max_norm, int skip, double *__restrict__ record)
+                                                                       float max_norm, int skip, double *__restrict__ record,
+                                                                       float *__restrict__ ema, float omd)
 {
     const double sumsq = gn_fold_partials(partials, parts);
     const float normf = (float)sqrt(sumsq);
@@ -142,7 +206,7 @@ __global__ __launch_bounds__(AD_THREADS) void adam_flat_guarded_kernel(int n_ten
         }
         record[5] = sumsq; record[6] = (double)normf; record[7] = (double)scale;
     }
-    if (nonfinite && skip) return;                             // before any store to p, m, v
+    if (nonfinite && skip) return;                             // before any store to p, m, v, ema
 
     const long long e0 = (long long)blockIdx.x * AD_CHUNK;
     int t = 0;
@@ -165,7 +229,9 @@ __global__ __launch_bounds__(AD_THREADS) void adam_flat_guarded_kernel(int n_ten
         const float vn = b2 * vv + b2w * (g * g);
         m[e] = mn; v[e] = vn;
         const float denom = sqrtf(vn) / bc2_sqrt + eps;
-        *p = pv - step_size * (mn / denom);
+        const float pn = pv - step_size * (mn / denom);
+        *p = pn;
+        if (EMA) { const float ev = ema[e]; ema[e] = fmaf(omd, pn - ev, ev); }
     }
 }
 
@@ -191,18 +257,38 @@ extern "C" int cmf_grad_norm(long long total, const float *grad, double *partial
     return cmf_launch_status();
 }
 
-extern "C" int cmf_adam_step_guarded(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad,
-                                     float *m, float *v, double lr, double beta1, double beta2, double eps, double weight_decay,
-                                     long long step, double max_grad_norm, int skip_nonfinite, const double *partials, double *record,
-                                     void *stream)
+static int adam_guarded_launch(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
+                               float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
+                               double max_grad_norm, int skip_nonfinite, const double *partials, double *record, float *ema,
+                               double ema_decay, void *stream)
 {
     CMF_CHECK_ARG(n_tensors > 0 && offsets && params && total > 0 && grad && m && v && step >= 1 && lr >= 0.0);
     CMF_CHECK_ARG(partials && record && ((uintptr_t)partials & 7) == 0 && ((uintptr_t)record & 7) == 0 && !std::isnan(max_grad_norm));
     const int clip_on = max_grad_norm > 0.0 && std::isfinite(max_grad_norm);
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_flat_guarded_kernel, dim3((unsigned)cmf_divup(total, AD_CHUNK)), dim3(AD_THREADS), 0, (hipStream_t)stream,
+    const auto kernel = ema ? adam_flat_guarded_kernel<true> : adam_flat_guarded_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)cmf_divup(total, AD_CHUNK)), dim3(AD_THREADS), 0, (hipStream_t)stream,
                        n_tensors, offsets, params, total, grad, m, v, (float)weight_decay, (float)(1.0 - beta1), (float)beta2,
                        (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps, partials, cmf_grad_norm_parts(total), clip_on,
-                       clip_on ? (float)max_grad_norm : 0.f, skip_nonfinite != 0, record);
+                       clip_on ? (float)max_grad_norm : 0.f, skip_nonfinite != 0, record, ema, ema ? (float)(1.0 - ema_decay) : 0.f);
     return cmf_launch_status();
+}
+
+extern "C" int cmf_adam_step_guarded(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad,
+                                     float *m, float *v, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                     long long step, double max_grad_norm, int skip_nonfinite, const double *partials, double *record,
+                                     void *stream)
+{
+    return adam_guarded_launch(n_tensors, offsets, params, total, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, max_grad_norm,
+                               skip_nonfinite, partials, record, nullptr, 0.0, stream);
+}
+
+extern "C" int cmf_adam_step_guarded_ema(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad,
+                                         float *m, float *v, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                         long long step, double max_grad_norm, int skip_nonfinite, const double *partials, double *record,
+                                         float *ema, double ema_decay, void *stream)
+{
+    if (int err = ema_check(ema, ema_decay)) return err;
+    return adam_guarded_launch(n_tensors, offsets, params, total, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, max_grad_norm,
+                               skip_nonfinite, partials, record, ema, ema_decay, stream);
 }

@@ -10,6 +10,7 @@ single ``all_reduce(SUM)`` per optimizer step and scaled by 1/world.  Nothing is
 the forward pass.  Parameters that never receive a gradient (the 12 unused WeightNet-BN
 tensors) stay outside the bucket with grad=None, so Adam skips them as it does in the reference.
 """
+import contextlib
 import math
 
 import torch
@@ -86,6 +87,16 @@ def guard_options(max_grad_norm=None, skip_nonfinite=False):
     return max_grad_norm, bool(skip_nonfinite)
 
 
+def ema_options(ema_decay=None):
+    """The decay of the averaged weights, checked: -> a float in the open interval (0, 1), or None (off).  A bool, 0, 1, a negative
+    number, NaN and inf raise ValueError: a decay of 0 is the live weights, a decay of 1 never moves, neither is an average."""
+    if ema_decay is None:
+        return None
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < float(ema_decay) < 1.0:
+        raise ValueError("ema_decay must be a number in the open interval (0, 1) or None, not %r" % (ema_decay,))
+    return float(ema_decay)
+
+
 def grad_norm(bucket):
     """The L2 norm of the bucket's gradient as a 0-d float64 device tensor: cmf_grad_norm, two launches on the current stream, no
     host read.  The sum of squares is accumulated in double over a partition that depends on the bucket's size alone, in a fixed
@@ -114,11 +125,22 @@ class FlatAdam(torch.optim.Optimizer):
     formula): the decision is taken on the device, the host reads nothing.  The bucket itself is NOT scaled -- it is zeroed before
     the next backward anyway -- so ``p.grad`` read after a clipped step holds the unclipped gradient.  ``steps`` counts calls: a
     skipped call advances the bias corrections like any other.  ``record`` (8 float64 on the device, see ``guard_stats``) counts
-    what the guard did.  Not guarded: BatchNorm's running statistics, which a train-mode forward has already updated."""
+    what the guard did.  Not guarded: BatchNorm's running statistics, which a train-mode forward has already updated.
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+    Averaged weights (off by default: ``ema_decay=None`` launches what it launched before).  With a decay d in (0, 1), ``ema`` is a
+    flat fp32 array in bucket order, set to the parameters at construction (so there is no debiasing), and ``step()`` calls
+    cmf_adam_step_ema / cmf_adam_step_guarded_ema: the same launch also does ``ema += float32(1 - d) * (p_new - ema)`` in one fma
+    (include/cmflow_hip.h has the formula and why this form).  Parameters and moments get the bits they get without it; a step the
+    guard skips leaves ``ema`` untouched as well.  ``ema_weights()`` runs the module on the average, ``ema_state_dict(module)`` is
+    the state dict to save.  BatchNorm's buffers are not averaged: the averaged parameters run with the live running statistics."""
+
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False,
+                 ema_decay=None):
         self.max_grad_norm, self.skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self.ema_decay = ema_options(ema_decay)
+        if self.ema_decay is not None and not bucket.flat.is_cuda:
+            raise ValueError("FlatAdam: ema_decay needs the GPU optimizer; the model is on the CPU")
         super().__init__(bucket.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise ValueError("FlatAdam: one parameter group (the bucket's parameters) -- per-group options are not supported")
@@ -133,6 +155,74 @@ class FlatAdam(torch.optim.Optimizer):
             parts = _lib.lib().cmf_grad_norm_parts(bucket.numel)
             self._partials = torch.zeros(parts, dtype=torch.float64, device=bucket.flat.device)
             self.record = torch.zeros(8, dtype=torch.float64, device=bucket.flat.device)
+        self._exchanged = False
+        if self.ema_decay is not None:
+            self.ema = torch.empty_like(bucket.flat)
+            self._ema_from_params()
+
+    def _ema_from_params(self):
+        """ema <- the parameters as they are now, slice by slice at the table's offsets."""
+        off = 0
+        with torch.no_grad():
+            for p in self.bucket.params:
+                n = p.numel()
+                self.ema[off:off + n].copy_(p.detach().reshape(-1))
+                off += n
+
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError("FlatAdam.%s: the averaged weights are off (ema_decay=None)" % what)
+
+    def _exchange(self):
+        from . import _lib
+        b = self.bucket
+        self._tables()
+        _lib.check(_lib.lib().cmf_param_exchange(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, self.ema.data_ptr(),
+                                                 _lib.stream_ptr()), "cmf_param_exchange")
+        bump = getattr(torch.autograd.graph, "increment_version", None)      # a raw-pointer write to the parameters, as in step()
+        if bump is not None:
+            bump(b.params)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Context manager: inside it the module computes with the averaged parameters.  One cmf_param_exchange launch on entry swaps
+        every parameter element with its ``ema`` element (``self.ema`` then holds the live parameters), one on exit -- in a
+        ``finally``, so also when the body raises -- swaps them back; pure copies, so everything is restored bit for bit.  Both
+        exchanges bump the parameters' autograd version counters as ``step()`` does.  Nested use and ``step()`` inside raise
+        RuntimeError.  BatchNorm's buffers are NOT averaged: the averaged parameters run with the live running statistics."""
+        self._need_ema("ema_weights")
+        if self._exchanged:
+            raise RuntimeError("FlatAdam.ema_weights: already inside ema_weights() (the parameters hold the averaged weights)")
+        self._exchange()
+        self._exchanged = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._exchanged = False
+
+    def ema_state_dict(self, module):
+        """``module.state_dict()`` with every bucket parameter replaced by a clone of its slice of ``ema``: the averaged model in the
+        module's own format (buffers and parameters outside the bucket are the live ones).  Slicing only: no exchange, no launch of
+        the library.  Raises inside ``ema_weights()``, where ``ema`` holds the live parameters."""
+        self._need_ema("ema_state_dict")
+        if self._exchanged:
+            raise RuntimeError("FlatAdam.ema_state_dict: inside ema_weights() self.ema holds the live parameters")
+        sd = module.state_dict()
+        slot = {}
+        off = 0
+        for p in self.bucket.params:
+            slot[id(p)] = (off, p)
+            off += p.numel()
+        found = 0
+        for name, p in module.named_parameters(remove_duplicate=False):
+            if id(p) in slot and name in sd:
+                o, q = slot[id(p)]
+                sd[name] = self.ema[o:o + q.numel()].view_as(q).clone()
+                found += 1
+        if found < len(slot):
+            raise ValueError("FlatAdam.ema_state_dict: the module's state dict holds %d of the bucket's %d parameters" % (found, len(slot)))
+        return sd
 
     def guard_stats(self, reset=False):
         """A copy of the guard's record, a float64 device tensor (no host read): [0] step() calls, [1] calls with a non-finite norm,
@@ -166,6 +256,8 @@ class FlatAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         from . import _lib
+        if self._exchanged:
+            raise RuntimeError("FlatAdam.step: inside ema_weights() the parameters hold the averaged weights")
         loss = closure() if closure is not None else None
         b = self.bucket
         for p, v in zip(b.params, b.views):
@@ -177,13 +269,22 @@ class FlatAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         self.steps += 1
         hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.steps)
+        averaged = self.ema_decay is not None
         if self.guarded:
             stream = _lib.stream_ptr()
             _lib.check(_lib.lib().cmf_grad_sumsq(b.numel, b.flat.data_ptr(), self._partials.data_ptr(), stream), "cmf_grad_sumsq")
-            _lib.check(_lib.lib().cmf_adam_step_guarded(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel,
-                                                        b.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *hyper,
-                                                        self.max_grad_norm or 0.0, int(self.skip_nonfinite), self._partials.data_ptr(),
-                                                        self.record.data_ptr(), stream), "cmf_adam_step_guarded")
+            args = (len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, b.flat.data_ptr(), self.exp_avg.data_ptr(),
+                    self.exp_avg_sq.data_ptr(), *hyper, self.max_grad_norm or 0.0, int(self.skip_nonfinite), self._partials.data_ptr(),
+                    self.record.data_ptr())
+            if averaged:
+                _lib.check(_lib.lib().cmf_adam_step_guarded_ema(*args, self.ema.data_ptr(), self.ema_decay, stream),
+                           "cmf_adam_step_guarded_ema")
+            else:
+                _lib.check(_lib.lib().cmf_adam_step_guarded(*args, stream), "cmf_adam_step_guarded")
+        elif averaged:
+            _lib.check(_lib.lib().cmf_adam_step_ema(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, b.flat.data_ptr(),
+                                                    self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *hyper, self.ema.data_ptr(),
+                                                    self.ema_decay, _lib.stream_ptr()), "cmf_adam_step_ema")
         else:
             _lib.check(_lib.lib().cmf_adam_step(len(b.params), self._offs.data_ptr(), self._pt.data_ptr(), b.numel, b.flat.data_ptr(),
                                                 self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *hyper, _lib.stream_ptr()),
@@ -203,6 +304,10 @@ class FlatAdam(torch.optim.Optimizer):
         d["flat"] = dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, steps=self.steps)
         if self.guarded:
             d["flat"]["guard"] = self.record
+        if self.ema_decay is not None:
+            if self._exchanged:
+                raise RuntimeError("FlatAdam.state_dict: inside ema_weights() self.ema holds the live parameters")
+            d["flat"]["ema"] = self.ema
         return d
 
     def load_state_dict(self, d):
@@ -212,7 +317,12 @@ class FlatAdam(torch.optim.Optimizer):
         indices are then positions in module.parameters(); the parameters outside the bucket (never used, frozen) have no state in
         such a checkpoint either and are skipped.  The moments are scattered into the flat arrays.  Anything else raises:
         restarting the moments silently would change the training run.  A guarded optimizer restores its record from
-        ``flat["guard"]`` and zeroes it for a checkpoint without one (the counters are diagnostics, not state of the run)."""
+        ``flat["guard"]`` and zeroes it for a checkpoint without one (the counters are diagnostics, not state of the run).
+        Averaged weights: with ``ema_decay`` set, ``flat["ema"]`` is restored; a checkpoint without it (any of the formats above)
+        re-initialises ``ema`` from the parameters as they are at load time -- load the model first; averaging starts from here (the
+        fine-tuning case).  With ``ema_decay=None`` a stored ``ema`` is ignored."""
+        if self._exchanged:
+            raise RuntimeError("FlatAdam.load_state_dict: inside ema_weights() the parameters hold the averaged weights")
         d = dict(d)
         flat = d.pop("flat", None)
         per_param = d.get("state") or {}
@@ -233,6 +343,11 @@ class FlatAdam(torch.optim.Optimizer):
                              % (len(saved), len(ps), self.bucket.module_params))
         group = dict(groups[0], params=list(range(len(ps))))
         super().load_state_dict(dict(d, state={}, param_groups=[group]))
+        if self.ema_decay is not None:
+            if flat is not None and "ema" in flat:
+                self.ema.copy_(flat["ema"])
+            else:
+                self._ema_from_params()
         if flat is not None:
             self.exp_avg.copy_(flat["exp_avg"]); self.exp_avg_sq.copy_(flat["exp_avg_sq"]); self.steps = int(flat["steps"])
             if self.guarded and "guard" in flat:

@@ -11,6 +11,7 @@ Around the step, on a ``dataset.DeviceSplit``: ``train_epoch`` / ``train_epoch_c
 ``train()`` (main.py:104-170): epochs, a validation epoch after each (``evaluate.eval_epoch`` / ``eval_epoch_clips``), StepLR,
 ``model.best.t7`` by validation RNE, and a resume point from which a run continues bit for bit.
 """
+import contextlib
 import math
 import os
 
@@ -18,19 +19,23 @@ import torch
 import torch.distributed as dist
 
 from . import synth
-from .dp import FlatAdam, FlatGradBucket, SegmentedReducer, guard_options
+from .dp import FlatAdam, FlatGradBucket, SegmentedReducer, ema_options, guard_options
 from .fused_blocks import join_side_streams
 from .losses import RadarFlowLoss, make_labels, make_labels_ragged
 
 
 class TrainStep:
     def __init__(self, net, vr_thres=0.3, lr=0.001, weight_decay=1e-4, camera_projection=None, t_camera_radar=None, group=None,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         """``max_grad_norm`` / ``skip_nonfinite``: the guard of the optimizer step (dp.FlatAdam) -- clip by the L2 norm of the whole
         gradient, leave parameters and moments untouched when that norm is not finite.  It runs inside ``opt.step()``, behind the
         all-reduce, so every rank sees the same bucket and takes the same decision without a further collective.  On a CPU model a
-        requested guard raises ValueError: torch's Adam has none and nothing here falls back."""
+        requested guard raises ValueError: torch's Adam has none and nothing here falls back.
+        ``ema_decay``: averaged weights (dp.FlatAdam: an exponential moving average of the parameters, updated inside the optimizer's
+        launch; ``opt.ema_weights()`` / ``opt.ema_state_dict(net)`` use it).  None: off, nothing changes.  Refused on a CPU model
+        like the guard."""
         max_grad_norm, skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
+        ema_decay = ema_options(ema_decay)
         self.net = net
         self.group = group                                         # the process group of the gradient all-reduce (None: the default one)
         dev = next(net.parameters()).device
@@ -42,7 +47,10 @@ class TrainStep:
         # tail of the step); on a CPU model torch's own
         if dev.type != "cuda" and (max_grad_norm is not None or skip_nonfinite):
             raise ValueError("TrainStep: max_grad_norm / skip_nonfinite need the GPU optimizer (dp.FlatAdam); the model is on the CPU")
-        self.opt = (FlatAdam(self.bucket, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        if dev.type != "cuda" and ema_decay is not None:
+            raise ValueError("TrainStep: ema_decay needs the GPU optimizer (dp.FlatAdam); the model is on the CPU")
+        self.opt = (FlatAdam(self.bucket, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                             ema_decay=ema_decay)
                     if dev.type == "cuda" else torch.optim.Adam(self.bucket.params, lr=lr, weight_decay=weight_decay))
         self.recurrent = hasattr(net, "gru")
         self.self_supervised = hasattr(net, "fd_layer")
@@ -279,7 +287,7 @@ def _refuse(net, train_split, val_split, epochs, rank, world, group):
 
 def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_points, lr=1e-3, decay_epochs=1, decay_rate=0.9,
         seed=1234, mini_clip_len=5, vr_thres=0.3, out_dir=None, resume=None, on_epoch=None, rank=0, world=1, group=None, args=None,
-        max_grad_norm=None, skip_nonfinite=False):
+        max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
     """The reference's ``train()`` (main.py:104-170) on two device-resident splits, without its plots and log files; the defaults
     are configs.yaml's.  One TrainStep (Adam, weight decay 1e-4) and one StepLR (``make_schedule``), then per epoch:
 
@@ -327,7 +335,18 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     with the guard off, history, record and ``last.pt`` have exactly the keys they had without it.  The guard protects parameters
     and moments; train-mode BatchNorm updates its running statistics in the forward, so a non-finite INPUT still reaches those.
 
-    Refused before anything is launched and before any mode changes: a bad ``max_grad_norm`` (ValueError), ``epochs < 1``, CMFlow_T with a split without clip ranges, a
+    Averaged weights.  ``ema_decay`` (a float in (0, 1); None: off) goes to the TrainStep (dp.FlatAdam keeps an exponential moving
+    average of the parameters inside the optimizer's launch).  With it on, the epoch's validation runs inside
+    ``step.opt.ema_weights()``, so ``val_score`` -- and with it ``best`` -- is the averaged model's, and ``model.best.t7`` is
+    ``step.opt.ema_state_dict(net)``: still the reference's file format and nothing else.  BatchNorm's buffers are not averaged;
+    the averaged parameters are validated and saved with the live running statistics.  ``last.pt`` stores the live model and the
+    optimizer state, which carries ``ema``, and the settings gain ``ema_decay``; a resume point without it compares as "off", a
+    mismatch either way raises ValueError, and a resumed run continues bit for bit, ``ema`` included.  With ``ema_decay=None``
+    history, record, settings and ``last.pt`` keep exactly their keys and the launches are the same.  Data parallel: nothing is
+    exchanged for it -- every rank's parameters are bit-identical (one averaged gradient), so every rank's ``ema`` is; each rank
+    swaps its own copy in for the validation and rank 0 writes.
+
+    Refused before anything is launched and before any mode changes: a bad ``max_grad_norm`` or ``ema_decay`` (ValueError), ``epochs < 1``, CMFlow_T with a split without clip ranges, a
     bad rank / world, ``world > 1`` without an initialised process group (ValueError); a model that is not CMFlow / CMFlow_T /
     RaFlow (NotImplementedError); a split or a network that is not on the GPU (RuntimeError).
     Whole-frame training (``epoch_ragged`` / ``step_ragged``) is not driven from here: its epoch 0 would need train-mode BatchNorm
@@ -335,6 +354,7 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     from . import evaluate as EV
     max_grad_norm, skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
     guarded = max_grad_norm is not None or skip_nonfinite
+    ema_decay = ema_options(ema_decay)
     recurrent, rank, world = _refuse(net, train_split, val_split, epochs, rank, world, group)
     dev = train_split.device
     settings = {"model": type(net).__name__, "batch_size": int(batch_size), "val_batch_size": int(val_batch_size),
@@ -343,17 +363,20 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
                 "train_frames": len(train_split), "val_frames": len(val_split)}
     if guarded:
         settings.update(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    if ema_decay is not None:
+        settings.update(ema_decay=ema_decay)
     state = None
     if resume is not None:
         state = torch.load(resume, map_location=dev)
         if not isinstance(state, dict) or state.get("format") != "cmflow_amd.fit" or state.get("version") != RESUME_VERSION:
             raise ValueError("fit: %s is not a resume point of format version %d" % (resume, RESUME_VERSION))
-        off = {"max_grad_norm": None, "skip_nonfinite": False}                       # a resume point without them: guard off
+        off = {"max_grad_norm": None, "skip_nonfinite": False, "ema_decay": None}    # a resume point without them: guard / average off
         stored, given = dict(off, **state["settings"]), dict(off, **settings)
         differ = {k: (stored.get(k), v) for k, v in given.items() if stored.get(k) != v}
         if differ:
             raise ValueError("fit: the resume point was written by a run with other settings (stored, given): %s" % differ)
-    step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                     ema_decay=ema_decay)
     scheduler = make_schedule(step.opt, decay_epochs, decay_rate)
     history = {"train_loss": [], "loss_items": [], "val_score": [], "lr": [], "best": math.inf}     # main.py:110
     if guarded:
@@ -376,12 +399,13 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
             total, items = train_epoch(step, train_split, batch_size, num_points, seed, epoch, rank, world)
         if world > 1:
             _broadcast_buffers(net, group)
-        if recurrent:
-            sf = EV.eval_epoch_clips(net, val_split, val_batch_size, mini_clip_len, num_points, seed + 1, epoch, args,
-                                     rank=rank, world=world, group=group)[0]
-        else:
-            sf = EV.eval_epoch(net, val_split, val_batch_size, num_points, seed + 1, epoch, args, rank=rank, world=world,
-                               group=group)[0]
+        with step.opt.ema_weights() if ema_decay is not None else contextlib.nullcontext():      # the averaged model is what is scored
+            if recurrent:
+                sf = EV.eval_epoch_clips(net, val_split, val_batch_size, mini_clip_len, num_points, seed + 1, epoch, args,
+                                         rank=rank, world=world, group=group)[0]
+            else:
+                sf = EV.eval_epoch(net, val_split, val_batch_size, num_points, seed + 1, epoch, args, rank=rank, world=world,
+                                   group=group)[0]
         stats = torch.stack([total, *items.values()])
         if world > 1:                                               # this rank's statistics -> the mean over the ranks
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
@@ -406,7 +430,7 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
         if is_best:
             history["best"] = score
             if writes:
-                save_atomic(net.state_dict(), os.path.join(out_dir, BEST_FILE))
+                save_atomic(net.state_dict() if ema_decay is None else step.opt.ema_state_dict(net), os.path.join(out_dir, BEST_FILE))
         scheduler.step()
         if writes:
             save_atomic({"format": "cmflow_amd.fit", "version": RESUME_VERSION, "settings": settings, "epoch": epoch + 1,

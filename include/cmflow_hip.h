@@ -515,6 +515,30 @@ int cmf_adam_step_guarded(int n_tensors, const long long *offsets, float *const 
                           float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
                           double max_grad_norm, int skip_nonfinite, const double *partials, double *record, void *stream);
 
+/* Averaged weights: an exponential moving average of the parameters, kept inside the optimizer's launch.
+ *
+ * cmf_adam_step_ema / cmf_adam_step_guarded_ema: cmf_adam_step / cmf_adam_step_guarded (the same kernels, instantiated with the average
+ * on; parameters and moments get the same bits) and, for every element, with pn the value just stored to the parameter and ev = ema[e]:
+ *     ema[e] = fmaf(omd, pn - ev, ev)                // omd = (float)(1.0 - ema_decay): formed in double on the host, rounded once
+ * one explicit fma, so the result does not depend on contraction.  The lerp form on purpose: its fixed point is pn itself (pn == ev gives
+ * ev back bit for bit), where d * ev + (1 - d) * pn carries a relative bias of order 2^-24 / (1 - d) -- 3e-5 at d = 0.999.
+ * ema: `total` floats in bucket order in device memory, 4-byte aligned like m and v; 0 < ema_decay < 1 (anything else, NaN included:
+ * hipErrorInvalidValue, nothing launched).  The caller initialises ema (to the parameters: no debiasing is then needed).
+ * Skip rule (guarded form): the return on a skipped step (non-finite norm and skip_nonfinite) is in front of EVERY store, the one to ema
+ * included -- a skipped step leaves p, m, v and ema untouched.  Without skip a NaN reaches ema[e] wherever it reaches the parameter.
+ *
+ * cmf_param_exchange: every parameter element is swapped with flat[e] (params[t][e - offsets[t]] <-> flat[e]) through the same address
+ * table and chunk walk as cmf_adam_step.  Pure copies: applied twice it is the identity, bit for bit.  flat: `total` floats in bucket
+ * order, 4-byte aligned.  One launch; run the model on the averaged weights between two calls with flat = ema. */
+int cmf_adam_step_ema(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m, float *v,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, long long step, float *ema, double ema_decay,
+                      void *stream);
+int cmf_adam_step_guarded_ema(int n_tensors, const long long *offsets, float *const *params, long long total, const float *grad, float *m,
+                              float *v, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
+                              double max_grad_norm, int skip_nonfinite, const double *partials, double *record, float *ema,
+                              double ema_decay, void *stream);
+int cmf_param_exchange(int n_tensors, const long long *offsets, float *const *params, long long total, float *flat, void *stream);
+
 /* Float offsets, inside `saved`, of the six per-layer BatchNorm blocks (mean | invstd | a | c, 4*C_l floats each). */
 int cmf_setconv_bn_offsets(const cmf_setconv_desc *d, long long *offsets6);
 
