@@ -208,6 +208,9 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
     float4 psa = make_float4(1.f, 1.f, 1.f, 1.f), psc = make_float4(0.f, 0.f, 0.f, 0.f);   // A prologue (per chunk)
     float4 qsa = make_float4(1.f, 1.f, 1.f, 1.f), qsc = make_float4(0.f, 0.f, 0.f, 0.f);   // B prologue (per thread)
     unsigned kmask = 0xF;                               // which of this thread's 4 k are < K (edge chunks)
+    // which of this thread's staged float4 lie outside the matrix (edge path: A rows m >= M, B rows k >= K) and must store zeros
+    // after a prologue: carried beside the data, never in it -- a NaN is a valid operand value and reaches C
+    unsigned adead = 0, bdead = 0;
     const bool proA = !A_T && p.pro_a != nullptr;
     const bool proB = !B_T && p.prob_a != nullptr;
     const bool edge_mn = (m0 + BM > p.M) || (n0 + BN > p.N);
@@ -259,6 +262,7 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
                 for (int i = 0; i < B_IT; ++i) rb[i] = *(const float4 *)(src + (long long)B_RPI * i * p.ldb);
             }
             kmask = 0xF;
+            adead = 0; bdead = 0;
             return;
         }
         if (GATHER_B) __builtin_trap();                         // (the host only sends full tiles and whole chunks)
@@ -274,11 +278,12 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
             const int kv = max(0, min(4, p.K - kk));
             kmask = (1u << kv) - 1u;
             if (proA) { psa = ld4(p.pro_a + kk, kv); psc = ld4(p.pro_c + kk, kv); }
+            adead = 0;
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const int m = m0 + (tid / G_KT) + G_RP * i;
                 ra[i] = (m < p.M && kv > 0) ? ld4(p.A + (long long)m * p.lda + kk, kv) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (m >= p.M) ra[i].x = __builtin_nanf("");            // marks a row that must store zeros
+                if (m >= p.M) adead |= 1u << i;                         // a row that must store zeros
             }
         } else {
 #pragma unroll
@@ -296,11 +301,12 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
                 rb[i] = (n < p.N && kv > 0) ? ld4(p.B + (long long)n * p.ldb + kk, kv) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         } else {
+            bdead = 0;
 #pragma unroll
             for (int i = 0; i < B_IT; ++i) {
                 const int k = k0 + tid / B_TPR + B_RPI * i, n = n0 + (tid % B_TPR) * 4;
                 rb[i] = (k < p.K && n < p.N) ? ld4(p.B + (long long)k * p.ldb + n, p.N - n) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!(k < p.K)) rb[i].x = __builtin_nanf("");          // out-of-range k row: must store zeros
+                if (!(k < p.K)) bdead |= 1u << i;                       // out-of-range k row: must store zeros
             }
         }
     };
@@ -315,13 +321,12 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 float4 v = ra[i];
-                if (proA) {
-                    const bool dead = v.x != v.x;                   // NaN marker from the edge path
+                if (proA) {                                         // (without a prologue the zero fill of the edge path is already the value)
                     v = pro4(v, psa, psc);
-                    if (dead) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if ((adead >> i) & 1u) v = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (kmask != 0xF) { if (!(kmask & 1)) v.x = 0.f; if (!(kmask & 2)) v.y = 0.f;
                                         if (!(kmask & 4)) v.z = 0.f; if (!(kmask & 8)) v.w = 0.f; }
-                } else if (v.x != v.x && edge_mn) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
                 *(float4 *)(dst + ((tid / G_KT) + G_RP * i) * G_LDS_LD + (tid % G_KT) * 4) = v;
             }
         } else {
@@ -358,11 +363,10 @@ __global__ __launch_bounds__(G_THREADS, (BM > 128 || BN > 128) ? 2 : 3) void gem
                     v.z += fmaf(gbw[2].z, d.z, fmaf(gbw[1].z, d.y, gbw[0].z * d.x)); v.w += fmaf(gbw[2].w, d.z, fmaf(gbw[1].w, d.y, gbw[0].w * d.x));
                 }
                 if (proB) {
-                    const bool dead = v.x != v.x;
                     v = pro4(v, qsa, qsc);
-                    if (dead) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if ((bdead >> i) & 1u) v = make_float4(0.f, 0.f, 0.f, 0.f);
                     // columns n >= N hold relu(qsc)=0-filled scale (qsa=1,qsc=0 -> relu(0)=0): already zero
-                } else if (v.x != v.x) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
                 *(float4 *)(dst + k * B_LD + n) = v;
             }
         }

@@ -104,7 +104,8 @@ def test_gemm_backward_modes_and_splitk(dev):
         dW = gemm(dZ, Zp, a_t=True, b_t=False, prob=(ea, ec), split_k=split)
         _check(dW, ref3, dZ.double().abs().t() @ X.double().abs(), tol=4e-6)
     dW2 = gemm(dZ, Zp, a_t=True, b_t=False, prob=(ea, ec), split_k=8)
-    assert torch.equal(dW, dW) and torch.equal(dW2, gemm(dZ, Zp, a_t=True, b_t=False, prob=(ea, ec), split_k=8))
+    assert torch.equal(dW, gemm(dZ, Zp, a_t=True, b_t=False, prob=(ea, ec), split_k=16))       # dW: the split_k = 16 call above
+    assert torch.equal(dW2, gemm(dZ, Zp, a_t=True, b_t=False, prob=(ea, ec), split_k=8))
 
 
 def test_gemm_throughput_report(dev):
