@@ -68,50 +68,58 @@ NUM_NB = (4, 8, 16)                          # csrc/loss.hip: the neighbour coun
 ITEM_KEYS = ('Loss', 'smoothnessLoss', 'chamferLoss', 'veloLoss', 'egoLoss', 'maskLoss', 'opticalLoss', 'superviseLoss')
 
 
+def _call_loss(ctx, d, name, size_name, sizes, outs, pred_f, pre_trans, mseg_pre, data, hyper):
+    """Fills what RadarLossDesc and RadarLossCountedDesc share -- input pointers, weights, hyper-parameters, the gradient buffers
+    (kept in ctx.grads), the workspace -- and calls ``name`` with ``size_name(*sizes, num_nb)`` floats of workspace (hyper["tiled"]:
+    ``name + "_tiled"`` with ``name + "_workspace_tiled"``).  outs: descriptor field -> output tensor."""
+    f32 = torch.float32
+    t = {k: v.contiguous() for k, v in data.items()}
+    pred_f = pred_f.contiguous()
+    pre_trans = pre_trans.contiguous() if pre_trans is not None else None
+    mseg_pre = mseg_pre.contiguous() if mseg_pre is not None else None
+    for k, v in list(t.items()) + [("pred_f", pred_f), ("pre_trans", pre_trans), ("mseg_pre", mseg_pre)]:
+        _lib.dev_ptr(v, torch.int32 if k in ("n1", "n2") else f32)       # device / dtype / density checks (no CPU fallback)
+    d.self_only = int(hyper.get("self_only", False))
+    d.pc1, d.pc2, d.pred_f, d.vel1 = t["pc1"].data_ptr(), t["pc2"].data_ptr(), pred_f.data_ptr(), t["vel1"].data_ptr()
+    if not d.self_only:
+        d.gt_f, d.mseg_pre, d.mseg_gt = t["gt_f"].data_ptr(), mseg_pre.data_ptr(), t["mseg_gt"].data_ptr()
+        d.dyn_mask, d.radar_u, d.radar_v = t["dyn_mask"].data_ptr(), t["radar_u"].data_ptr(), t["radar_v"].data_ptr()
+        d.opt, d.pre_trans, d.gt_trans = t["opt"].data_ptr(), pre_trans.data_ptr(), t["gt_trans"].data_ptr()
+        d.camera_inverse, d.t_camera_radar = t["camera_inverse"].data_ptr(), t["t_camera_radar"].data_ptr()
+    d.w_self, d.w_em, d.w_ms, d.w_opt, d.w_dyn = hyper["w"]
+    d.zeta, d.alpha, d.num_nb, d.lower_bound = hyper["zeta"], hyper["alpha"], hyper["num_nb"], hyper["lower_bound"]
+    for field, out in outs.items():
+        setattr(d, field, out.data_ptr())
+    tiled = bool(hyper.get("tiled", False))                  # tests: the tiled kernels at a size the LDS kernel would take
+    L = _lib.lib()
+    size = getattr(L, name + "_workspace_tiled" if tiled else size_name)
+    ws = torch.empty(size(*sizes, int(hyper["num_nb"])), dtype=f32, device=pred_f.device)
+    d.workspace = ws.data_ptr()
+    if any(ctx.needs_input_grad[:3]):
+        g_f = torch.empty(pred_f.shape, dtype=f32, device=pred_f.device)
+        g_t = torch.empty(pred_f.shape[0], 4, 4, dtype=f32, device=pred_f.device) if pre_trans is not None else None
+        g_m = torch.empty(mseg_pre.shape, dtype=f32, device=pred_f.device) if mseg_pre is not None else None
+        d.d_pred_f = g_f.data_ptr()
+        d.d_pre_trans = g_t.data_ptr() if g_t is not None else None
+        d.d_mseg_pre = g_m.data_ptr() if g_m is not None else None
+        ctx.grads = (g_f, g_t, g_m)
+    call = getattr(L, name + "_tiled" if tiled else name)
+    _lib.check(call(ctypes.addressof(d), _lib.stream_ptr()), name)
+    ctx.mark_non_differentiable(*outs.values())
+
+
 class RadarFlowLossFn(Function):
     """total, items = cmf_radar_loss(...); the kernel writes d total / d (pred_f, pre_trans, mseg_pre) in the same
     pass, backward only scales them by the incoming gradient."""
 
     @staticmethod
     def forward(ctx, pred_f, pre_trans, mseg_pre, data, hyper):
-        pc1 = data["pc1"]
-        B, _, N = pc1.shape
-        dev = pc1.device
-        f32 = torch.float32
-        t = {k: v.contiguous() for k, v in data.items()}
-        pred_f = pred_f.contiguous()
-        pre_trans = pre_trans.contiguous() if pre_trans is not None else None
-        mseg_pre = mseg_pre.contiguous() if mseg_pre is not None else None
-        for v in list(t.values()) + [pred_f, pre_trans, mseg_pre]:
-            _lib.dev_ptr(v, f32)                                  # device / dtype / density checks (no CPU fallback)
-        need = any(ctx.needs_input_grad[:3])
+        B, _, N = data["pc1"].shape
+        items = torch.empty(9, dtype=torch.float32, device=data["pc1"].device)
         d = _lib.RadarLossDesc()
         d.B, d.N = B, N
-        d.self_only = int(hyper.get("self_only", False))
-        d.pc1, d.pc2, d.pred_f, d.vel1 = t["pc1"].data_ptr(), t["pc2"].data_ptr(), pred_f.data_ptr(), t["vel1"].data_ptr()
-        if not d.self_only:
-            d.gt_f, d.mseg_pre, d.mseg_gt = t["gt_f"].data_ptr(), mseg_pre.data_ptr(), t["mseg_gt"].data_ptr()
-            d.dyn_mask, d.radar_u, d.radar_v = t["dyn_mask"].data_ptr(), t["radar_u"].data_ptr(), t["radar_v"].data_ptr()
-            d.opt, d.pre_trans, d.gt_trans = t["opt"].data_ptr(), pre_trans.data_ptr(), t["gt_trans"].data_ptr()
-            d.camera_inverse, d.t_camera_radar = t["camera_inverse"].data_ptr(), t["t_camera_radar"].data_ptr()
-        d.w_self, d.w_em, d.w_ms, d.w_opt, d.w_dyn = hyper["w"]
-        d.zeta, d.alpha, d.num_nb, d.lower_bound = hyper["zeta"], hyper["alpha"], hyper["num_nb"], hyper["lower_bound"]
-        items = torch.empty(9, dtype=f32, device=dev)
-        tiled = bool(hyper.get("tiled", False))              # tests: the tiled kernels at a size the LDS kernel would take
-        size = _lib.lib().cmf_radar_loss_workspace_tiled if tiled else _lib.lib().cmf_radar_loss_workspace_nb
-        ws = torch.empty(size(B, N, int(hyper["num_nb"])), dtype=f32, device=dev)
-        d.items, d.workspace = items.data_ptr(), ws.data_ptr()
-        if need:
-            g_f = torch.empty(B, 3, N, dtype=f32, device=dev)
-            g_t = torch.empty(B, 4, 4, dtype=f32, device=dev) if pre_trans is not None else None
-            g_m = torch.empty(mseg_pre.shape, dtype=f32, device=dev) if mseg_pre is not None else None
-            d.d_pred_f = g_f.data_ptr()
-            d.d_pre_trans = g_t.data_ptr() if g_t is not None else None
-            d.d_mseg_pre = g_m.data_ptr() if g_m is not None else None
-            ctx.grads = (g_f, g_t, g_m)
-        call = _lib.lib().cmf_radar_loss_tiled if tiled else _lib.lib().cmf_radar_loss
-        _lib.check(call(ctypes.addressof(d), _lib.stream_ptr()), "cmf_radar_loss")
-        ctx.mark_non_differentiable(items)
+        _call_loss(ctx, d, "cmf_radar_loss", "cmf_radar_loss_workspace_nb", (B, N), dict(items=items), pred_f, pre_trans, mseg_pre,
+                   data, hyper)
         return items[0], items
 
     @staticmethod
@@ -134,47 +142,16 @@ class RadarFlowLossRaggedFn(Function):
 
     @staticmethod
     def forward(ctx, pred_f, pre_trans, mseg_pre, data, hyper):
-        pc1, pc2, n1, n2 = data["pc1"], data["pc2"], data["n1"], data["n2"]
-        B, _, N1 = pc1.shape
-        N2 = pc2.shape[2]
-        dev = pc1.device
-        f32 = torch.float32
-        t = {k: v.contiguous() for k, v in data.items()}
-        pred_f = pred_f.contiguous()
-        pre_trans = pre_trans.contiguous() if pre_trans is not None else None
-        mseg_pre = mseg_pre.contiguous() if mseg_pre is not None else None
-        for k, v in list(t.items()) + [("pred_f", pred_f), ("pre_trans", pre_trans), ("mseg_pre", mseg_pre)]:
-            _lib.dev_ptr(v, torch.int32 if k in ("n1", "n2") else f32)   # device / dtype / density checks (no CPU fallback)
-        need = any(ctx.needs_input_grad[:3])
+        B, _, N1 = data["pc1"].shape
+        N2 = data["pc2"].shape[2]
+        per_sample = torch.empty(B, 9, dtype=torch.float32, device=data["pc1"].device)
+        items = torch.empty(9, dtype=torch.float32, device=data["pc1"].device)
+        n1, n2 = data["n1"].contiguous(), data["n2"].contiguous()
         d = _lib.RadarLossCountedDesc()
         d.B, d.N1max, d.N2max = B, N1, N2
-        d.n1, d.n2 = t["n1"].data_ptr(), t["n2"].data_ptr()
-        d.self_only = int(hyper.get("self_only", False))
-        d.pc1, d.pc2, d.pred_f, d.vel1 = t["pc1"].data_ptr(), t["pc2"].data_ptr(), pred_f.data_ptr(), t["vel1"].data_ptr()
-        if not d.self_only:
-            d.gt_f, d.mseg_pre, d.mseg_gt = t["gt_f"].data_ptr(), mseg_pre.data_ptr(), t["mseg_gt"].data_ptr()
-            d.dyn_mask, d.radar_u, d.radar_v = t["dyn_mask"].data_ptr(), t["radar_u"].data_ptr(), t["radar_v"].data_ptr()
-            d.opt, d.pre_trans, d.gt_trans = t["opt"].data_ptr(), pre_trans.data_ptr(), t["gt_trans"].data_ptr()
-            d.camera_inverse, d.t_camera_radar = t["camera_inverse"].data_ptr(), t["t_camera_radar"].data_ptr()
-        d.w_self, d.w_em, d.w_ms, d.w_opt, d.w_dyn = hyper["w"]
-        d.zeta, d.alpha, d.num_nb, d.lower_bound = hyper["zeta"], hyper["alpha"], hyper["num_nb"], hyper["lower_bound"]
-        per_sample = torch.empty(B, 9, dtype=f32, device=dev)
-        items = torch.empty(9, dtype=f32, device=dev)
-        tiled = bool(hyper.get("tiled", False))
-        size = _lib.lib().cmf_radar_loss_counted_workspace_tiled if tiled else _lib.lib().cmf_radar_loss_counted_workspace
-        ws = torch.empty(size(B, N1, N2, int(hyper["num_nb"])), dtype=f32, device=dev)
-        d.items, d.items_mean, d.workspace = per_sample.data_ptr(), items.data_ptr(), ws.data_ptr()
-        if need:
-            g_f = torch.empty(B, 3, N1, dtype=f32, device=dev)
-            g_t = torch.empty(B, 4, 4, dtype=f32, device=dev) if pre_trans is not None else None
-            g_m = torch.empty(mseg_pre.shape, dtype=f32, device=dev) if mseg_pre is not None else None
-            d.d_pred_f = g_f.data_ptr()
-            d.d_pre_trans = g_t.data_ptr() if g_t is not None else None
-            d.d_mseg_pre = g_m.data_ptr() if g_m is not None else None
-            ctx.grads = (g_f, g_t, g_m)
-        call = _lib.lib().cmf_radar_loss_counted_tiled if tiled else _lib.lib().cmf_radar_loss_counted
-        _lib.check(call(ctypes.addressof(d), _lib.stream_ptr()), "cmf_radar_loss_counted")
-        ctx.mark_non_differentiable(items, per_sample)
+        d.n1, d.n2 = n1.data_ptr(), n2.data_ptr()
+        _call_loss(ctx, d, "cmf_radar_loss_counted", "cmf_radar_loss_counted_workspace", (B, N1, N2),
+                   dict(items=per_sample, items_mean=items), pred_f, pre_trans, mseg_pre, data, hyper)
         return items[0], items, per_sample
 
     @staticmethod
@@ -214,18 +191,24 @@ class RadarFlowLoss(Module):
         """With only (pc1, pc2, pred_f, vel1) this is the loss of model 'raflow' (radar_loss.py:274-276): the three
         self-supervised terms; items then has the four keys of SelfSupervisedLoss (:153-158)."""
         self._check(pc1)
+        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt)
         if gt_f is None:
-            hyper = dict(w=(self.w_self, 0.0, 0.0, 0.0, 0.0), zeta=self.zeta, alpha=self.alpha, num_nb=self.num_nb,
-                         lower_bound=0.0, self_only=True, tiled=self.tiled)
-            total, items = RadarFlowLossFn.apply(pred_f, None, None, dict(pc1=pc1, pc2=pc2, vel1=vel1), hyper)
-            return total, {k: items[i + 1] for i, k in enumerate(SELF_ITEM_KEYS)}
+            pre_trans = mseg_pre = None
+        total, items = RadarFlowLossFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
+        return total, {k: items[i + 1] for i, k in enumerate(keys)}
+
+    def _data_hyper(self, pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt):
+        """-> the Functions' data and hyper dictionaries and the keys of the reported items; without gt_f the self-only case"""
+        if gt_f is None:
+            return dict(pc1=pc1, pc2=pc2, vel1=vel1), dict(
+                w=(self.w_self, 0.0, 0.0, 0.0, 0.0), zeta=self.zeta, alpha=self.alpha, num_nb=self.num_nb, lower_bound=0.0,
+                self_only=True, tiled=self.tiled), SELF_ITEM_KEYS
         data = dict(pc1=pc1, pc2=pc2, gt_f=gt_f, vel1=vel1, gt_trans=gt_trans, mseg_gt=mseg_gt.to(pc1.dtype),
                     dyn_mask=dyn_mask.to(pc1.dtype), radar_u=radar_u, radar_v=radar_v, opt=opt,
                     camera_inverse=self.camera_inverse, t_camera_radar=self.t_camera_radar)
         hyper = dict(w=(self.w_self, self.w_em, self.w_ms, self.w_opt, self.w_dyn), zeta=self.zeta, alpha=self.alpha,
                      num_nb=self.num_nb, lower_bound=self.lower_bound, tiled=self.tiled)
-        total, items = RadarFlowLossFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
-        return total, {k: items[i + 1] for i, k in enumerate(ITEM_KEYS)}
+        return data, hyper, ITEM_KEYS
 
     # ---- ragged batches: whole frames of their own sizes (CMFlow.forward_ragged, dataset.collate_ragged) ----------------------------
     def _check_ragged(self, pc1, pc2, pred_f, npoints1, npoints2, validate):
@@ -264,16 +247,8 @@ class RadarFlowLoss(Module):
         they are trusted: the kernels clamp them to [num_nb + 1, Nmax1] / [1, Nmax2], so a wrong count gives wrong numbers, not a
         wild access.  Without gt_f: the three self-supervised terms (model 'raflow'), as in ``forward``."""
         self._check_ragged(pc1, pc2, pred_f, npoints1, npoints2, validate)
+        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt)
         if gt_f is None:
-            hyper = dict(w=(self.w_self, 0.0, 0.0, 0.0, 0.0), zeta=self.zeta, alpha=self.alpha, num_nb=self.num_nb,
-                         lower_bound=0.0, self_only=True, tiled=self.tiled)
-            total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, None, None, dict(pc1=pc1, pc2=pc2, vel1=vel1, n1=npoints1,
-                                                                                            n2=npoints2), hyper)
-            return total, {k: items[i + 1] for i, k in enumerate(SELF_ITEM_KEYS)}, per_sample
-        data = dict(pc1=pc1, pc2=pc2, gt_f=gt_f, vel1=vel1, gt_trans=gt_trans, mseg_gt=mseg_gt.to(pc1.dtype),
-                    dyn_mask=dyn_mask.to(pc1.dtype), radar_u=radar_u, radar_v=radar_v, opt=opt,
-                    camera_inverse=self.camera_inverse, t_camera_radar=self.t_camera_radar, n1=npoints1, n2=npoints2)
-        hyper = dict(w=(self.w_self, self.w_em, self.w_ms, self.w_opt, self.w_dyn), zeta=self.zeta, alpha=self.alpha,
-                     num_nb=self.num_nb, lower_bound=self.lower_bound, tiled=self.tiled)
-        total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
-        return total, {k: items[i + 1] for i, k in enumerate(ITEM_KEYS)}, per_sample
+            pre_trans = mseg_pre = None
+        total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, pre_trans, mseg_pre, dict(data, n1=npoints1, n2=npoints2), hyper)
+        return total, {k: items[i + 1] for i, k in enumerate(keys)}, per_sample

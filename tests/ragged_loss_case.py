@@ -1,5 +1,5 @@
 """The ragged batches of tests/test_gpu_ragged_loss.py and tests/test_ragged_loss_host.py (a test fixture, not a test): B synthetic
-frames with their own point counts -- sample i of synth.make_batch(B, 300, seed, train_extras=True) truncated to (n1, n2) -- plus
+frames with their own point counts -- sample i of synth.make_batch(B, full, seed, train_extras=True) truncated to (n1, n2) -- plus
 network-output stand-ins as tests/test_gpu_loss.py::_case builds them, padded to (nmax1, nmax2) with large finite garbage."""
 import torch
 
@@ -10,20 +10,23 @@ COUNTS6 = ((256, 256), (211, 187), (97, 130), (130, 130), (64, 40), (33, 9))
 COUNTS5 = ((256, 256), (211, 187), (130, 130), (64, 40), (33, 9))        # B not a power of two
 SEED6, SEED5 = 2, 3              # seeds for which every truncated sample holds both motion-seg classes and a dynamic point
 #                                  (tests/test_ragged_loss_host.py asserts it on the oracle's labels)
-POINT_KEYS1 = ("pc1", "ft1", "pred_f", "gt_f", "mseg_pre")               # (B,C,N1) channel-major
+# the LDS form above 512 points, where pass 3 scans and keeps no inverse list: frames of 600 points padded to (600, 600); three samples
+# with n1 == n2, 257 puts one point into a thread's second slot, (9, 9) is the smallest size both forms accept
+COUNTS4, SEED4, FULL4 = ((600, 600), (513, 513), (257, 300), (9, 9)), 4, 600
+POINT_KEYS1 =("pc1", "ft1", "pred_f", "gt_f", "mseg_pre")               # (B,C,N1) channel-major
 ROW_KEYS1 = ("flow_label", "fg_mask", "radar_u", "radar_v", "opt_flow")  # (B,N1[,C]) point-major
 
 
-def make_case(counts, seed):
-    """-> (batch, outs): dicts of CPU tensors at the full size 300 (nothing truncated or padded yet)."""
+def make_case(counts, seed, full=300):
+    """-> (batch, outs): dicts of CPU tensors at the full size (nothing truncated or padded yet)."""
     B = len(counts)
-    batch = synth.make_batch(B, 300, seed=seed, train_extras=True)
+    batch = synth.make_batch(B, full, seed=seed, train_extras=True)
     g = torch.Generator().manual_seed(seed + 7)
     gt_f = batch["flow_label"].transpose(2, 1).contiguous()
-    pred_f = gt_f + 0.3 * torch.randn(B, 3, 300, generator=g)
+    pred_f = gt_f + 0.3 * torch.randn(B, 3, full, generator=g)
     pre_trans = batch["gt_trans"].clone()
     pre_trans[:, :3, :] += 0.01 * torch.randn(B, 3, 4, generator=g)
-    mseg_pre = torch.sigmoid(2.0 * torch.randn(B, 1, 300, generator=g))
+    mseg_pre = torch.sigmoid(2.0 * torch.randn(B, 1, full, generator=g))
     return batch, dict(pred_f=pred_f, pre_trans=pre_trans, mseg_pre=mseg_pre)
 
 

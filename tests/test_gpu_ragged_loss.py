@@ -67,16 +67,18 @@ def _slices(grads, i, n1):
     return gf[i, :, :n1], (gt[i] if gt is not None else None), (gm[i, :, :n1] if gm is not None else None)
 
 
-@pytest.mark.parametrize("counts,seed", CASES)
+@pytest.mark.parametrize("counts,seed", CASES + [(RC.COUNTS4, RC.SEED4)])
 @pytest.mark.parametrize("tiled", [False, True])
 @pytest.mark.parametrize("self_only", [False, True])
 def test_counted_loss_equals_the_dense_kernel_bit_for_bit(dev, counts, seed, tiled, self_only):
     """Check 1: samples with n1 == n2 -- per_sample[i] == the dense loss at B = 1 on the truncated sample, bit for bit, both forms,
     full loss and self_only.  The kernel multiplies by 1/B last: B = 6 -> one rounding of 1/B and one of the product (rtol 2**-22
-    on the gradient times B in float64); padded gradient slots are exactly 0."""
+    on the gradient times B in float64); padded gradient slots are exactly 0.  COUNTS4, padded to (600, 600), is the LDS form
+    above 512 points: pass 3 by the scan, not the inverse list."""
     B = len(counts)
-    batch, outs = RC.make_case(counts, seed)
-    pb, po = RC.padded(batch, outs, counts, 300, 256)
+    full, nmax1, nmax2 = (RC.FULL4, RC.FULL4, RC.FULL4) if counts is RC.COUNTS4 else (300, 300, 256)
+    batch, outs = RC.make_case(counts, seed, full)
+    pb, po = RC.padded(batch, outs, counts, nmax1, nmax2)
     crit = RadarFlowLoss(synth.CAMERA_PROJECTION, synth.T_CAMERA_RADAR).to(dev)
     crit.tiled = tiled
     total, items, per, leaves, _ = _run_ragged(crit, pb, po, dev, self_only)

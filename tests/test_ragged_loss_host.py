@@ -134,3 +134,12 @@ def test_oracle_is_finite_on_every_sample_of_the_gpu_tests_batches(counts, seed)
         assert all(torch.isfinite(g).all().item() for g in (pf.grad, pt.grad, pm.grad)), i
         st, sitems = TO.self_supervised_loss(b, o["pred_f"])
         assert torch.isfinite(st).item(), i
+
+
+def test_the_600_point_case_holds_both_classes_in_every_sample():
+    """The same precondition for RC.COUNTS4, down to its sample of 9 points: no empty motion-seg class, a dynamic point."""
+    assert sum(a == b for a, b in RC.COUNTS4) >= 2
+    batch, outs = RC.make_case(RC.COUNTS4, RC.SEED4, RC.FULL4)
+    for i in range(len(RC.COUNTS4)):
+        dyn, mseg = TO.make_labels(RC.sample(batch, outs, RC.COUNTS4, i)[0])
+        assert int((mseg == 0).sum()) >= 1 and int((mseg == 1).sum()) >= 1 and int((dyn == 0).sum()) >= 1, i
