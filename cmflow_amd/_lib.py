@@ -151,6 +151,7 @@ SIGNATURES = {
                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_draw_frames": [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cmf_augment_batch": [_ci, _ci, _ci, _ci, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_double, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_prepare_count": [_ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "cmf_prepare_scans": [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "cmf_prepare_pairs": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp],
@@ -206,7 +207,8 @@ class RadarLossDesc(ctypes.Structure):
                 ("opt", _vp), ("pre_trans", _vp), ("gt_trans", _vp), ("camera_inverse", _vp), ("t_camera_radar", _vp),
                 ("w_self", _cf), ("w_em", _cf), ("w_ms", _cf), ("w_opt", _cf), ("w_dyn", _cf),
                 ("zeta", _cf), ("alpha", _cf), ("num_nb", _ci), ("lower_bound", _cf), ("self_only", _ci),
-                ("items", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp)]
+                ("items", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp),
+                ("t_camera_radar_batch", _vp)]
 
 
 class RadarLossCountedDesc(ctypes.Structure):
@@ -217,7 +219,8 @@ class RadarLossCountedDesc(ctypes.Structure):
                 ("opt", _vp), ("pre_trans", _vp), ("gt_trans", _vp), ("camera_inverse", _vp), ("t_camera_radar", _vp),
                 ("w_self", _cf), ("w_em", _cf), ("w_ms", _cf), ("w_opt", _cf), ("w_dyn", _cf),
                 ("zeta", _cf), ("alpha", _cf), ("num_nb", _ci), ("lower_bound", _cf), ("self_only", _ci),
-                ("items", _vp), ("items_mean", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp)]
+                ("items", _vp), ("items_mean", _vp), ("d_pred_f", _vp), ("d_pre_trans", _vp), ("d_mseg_pre", _vp), ("workspace", _vp),
+                ("t_camera_radar_batch", _vp)]
 
 
 def build(force: bool = False) -> str:

@@ -14,40 +14,13 @@
 //
 // cmf_draw_frames (below, same tables): the frames themselves, whole and unsampled, padded to a ragged batch.
 #include "cmf_common.h"
+#include "philox.h"
 #include "../../include/cmflow_hip.h"
 
 namespace {
 
 constexpr int DRAW_COLS1 = 14, DRAW_COLS2 = 6;
 constexpr int DRAW_THREADS_SMALL = 256, DRAW_THREADS_LARGE = 1024;     // the large form from 4096 sort slots on
-
-struct Philox { uint32_t x, y, z, w; };
-
-__host__ __device__ inline uint32_t draw_mulhi(uint32_t a, uint32_t b)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    return __umulhi(a, b);
-#else
-    return (uint32_t)(((unsigned long long)a * b) >> 32);
-#endif
-}
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): ten rounds of two 32 x 32 -> 64 multiplies, key bumped by the Weyl constants
-__host__ __device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
-{
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = draw_mulhi(M0, c0), l0 = M0 * c0, h1 = draw_mulhi(M1, c2), l1 = M1 * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += W0;
-        k1 += W1;
-    }
-    return Philox{c0, c1, c2, c3};
-}
 
 struct DrawArgs {
     int B, N, F, max_points;
@@ -230,7 +203,7 @@ extern "C" int cmf_draw_batch_at(int slot0, int B, int npoints, int nframes, int
         if (e != hipSuccess) return (int)e;
         attr_set.done(attr_dev);
     }
-    const Philox key = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), 0u, 0u);
+    const Philox key = philox_call_key(seed, draw);
     DrawArgs a{B, npoints, nframes, max_points, slot0, tab1, tab2, off1, off2, trans, interval, frames, key.x, key.y,
                pc1, pc2, ft1, ft2, gt_trans, flow_label, fg_mask, interval_out, radar_u, radar_v, opt_flow, idx1, idx2};
     const int threads = P >= 4096 ? DRAW_THREADS_LARGE : DRAW_THREADS_SMALL;

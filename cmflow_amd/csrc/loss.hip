@@ -125,6 +125,7 @@ struct LossArgs {
     int B, N;
     const float *pc1, *pc2, *pred_f, *gt_f, *vel1, *mseg_pre, *mseg_gt, *dyn_mask, *radar_u, *radar_v, *opt;
     const float *pre_trans, *gt_trans, *cam_inv, *t_cr;
+    int t_cr_stride;            // 0: t_cr is the one shared matrix; 16: sample i takes row i (t_camera_radar_batch)
     float w_self, w_em, w_ms, w_opt, w_dyn, zeta, alpha, lower_bound;
     int self_only;
     int use_inv;                // pass 3 through an inverse list of the pushed gradients (N <= LS_INV_MAX_N)
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(LS_THREADS) void loss_sample_kernel(const LossArgs 
     if (!a.self_only) {
         if (tid < 16) { sT[tid] = a.pre_trans[(size_t)bs * 16 + tid]; sT[16 + tid] = a.gt_trans[(size_t)bs * 16 + tid]; }
         if (tid < 9) sC[tid] = a.cam_inv[tid];
-        if (tid >= 32 && tid < 48) sC[9 + tid - 32] = a.t_cr[tid - 32];
+        if (tid >= 32 && tid < 48) sC[9 + tid - 32] = a.t_cr[(size_t)bs * a.t_cr_stride + tid - 32];
     }
     __syncthreads();
     for (int i = tid; i < N; i += LS_THREADS) {
@@ -682,7 +683,7 @@ __global__ __launch_bounds__(LG_THREADS) void loss_big_sample_kernel(const LossA
     if (!a.self_only) {
         if (tid < 16) { sT[tid] = a.pre_trans[(size_t)bs * 16 + tid]; sT[16 + tid] = a.gt_trans[(size_t)bs * 16 + tid]; }
         if (tid < 9) sC[tid] = a.cam_inv[tid];
-        if (tid >= 32 && tid < 48) sC[9 + tid - 32] = a.t_cr[tid - 32];
+        if (tid >= 32 && tid < 48) sC[9 + tid - 32] = a.t_cr[(size_t)bs * a.t_cr_stride + tid - 32];
     }
     __syncthreads();
     const float inv_bn = 1.0f / ((float)(COUNTED ? 1 : a.B) * (float)N1);
@@ -924,7 +925,8 @@ static int loss_fill_args(const Desc *d, int n, size_t ncounts, LossArgs &a)
     a.B = d->B; a.N = n;
     a.pc1 = d->pc1; a.pc2 = d->pc2; a.pred_f = d->pred_f; a.gt_f = d->gt_f; a.vel1 = d->vel1; a.mseg_pre = d->mseg_pre;
     a.mseg_gt = d->mseg_gt; a.dyn_mask = d->dyn_mask; a.radar_u = d->radar_u; a.radar_v = d->radar_v; a.opt = d->opt;
-    a.pre_trans = d->pre_trans; a.gt_trans = d->gt_trans; a.cam_inv = d->camera_inverse; a.t_cr = d->t_camera_radar;
+    a.pre_trans = d->pre_trans; a.gt_trans = d->gt_trans; a.cam_inv = d->camera_inverse;
+    a.t_cr = d->t_camera_radar_batch ? d->t_camera_radar_batch : d->t_camera_radar; a.t_cr_stride = d->t_camera_radar_batch ? 16 : 0;
     a.w_self = d->w_self; a.w_em = d->w_em; a.w_ms = d->w_ms; a.w_opt = d->w_opt; a.w_dyn = d->w_dyn;
     a.zeta = d->zeta; a.alpha = d->alpha; a.lower_bound = d->lower_bound; a.self_only = d->self_only;
     a.use_inv = n <= LS_INV_MAX_N ? 1 : 0;

@@ -15,6 +15,7 @@ One sample = one JSON file ``<root>/<partition>/<clip>/<k>_*.json`` with
 run reproduces the reference's batches).  The calibration constants are those of dataset/vod_radar_calib.txt.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -228,6 +229,77 @@ def as_batch_dict_ragged(info):
     return d
 
 
+class Augment(tuple):
+    """The settings of the label-consistent augmentation (``augment_batch``): ``yaw_deg``, the largest
+    rotation about the sensor's z axis in degrees (0 <= yaw_deg < 180; 0: no rotation), and ``mirror``, whether a slot's y axis is
+    mirrored with probability 1/2.  Immutable; it IS the tuple ``(yaw_deg, mirror)`` -- it compares equal to it, and ``tuple(a)`` is
+    what a resume point stores.  A negative, non-finite or >= 180 ``yaw_deg`` raises ValueError."""
+    __slots__ = ()
+
+    def __new__(cls, yaw_deg=0.0, mirror=False):
+        try:
+            yaw = float(yaw_deg)
+        except (TypeError, ValueError):
+            raise ValueError("Augment: yaw_deg = %r is not a number" % (yaw_deg,))
+        if not (math.isfinite(yaw) and 0.0 <= yaw < 180.0):
+            raise ValueError("Augment: yaw_deg = %r; a finite number of degrees in [0, 180)" % (yaw_deg,))
+        return tuple.__new__(cls, (yaw, bool(mirror)))
+
+    def __getnewargs__(self):
+        return (self[0], self[1])
+
+    yaw_deg = property(lambda self: self[0])
+    mirror = property(lambda self: self[1])
+
+    @property
+    def tan_half_max(self):
+        """tan(yaw_max / 2), the one number cmf_augment_batch takes for the angle (computed here, once, in float64)."""
+        return math.tan(math.radians(self[0]) / 2.0)
+
+    def __repr__(self):
+        return "Augment(yaw_deg=%r, mirror=%r)" % (self[0], self[1])
+
+
+def augment_batch(batch, augment, seed, aug_draw, slot0=0, t_camera_radar=None):
+    """One transform per slot of an already drawn batch, IN PLACE, in one launch (cmf_augment_batch): a rotation about the sensor's z
+    axis by an angle within ``augment.yaw_deg`` after, with ``augment.mirror``, a mirror of the y axis in half of the slots -- the
+    transforms under which every label this model trains on stays consistent.  ``batch``: any batch dict on
+    the GPU -- ``as_batch_dict``, ``as_batch_dict_ragged``, a ``DeviceSplit.draw`` or ``draw_frames`` result; its ``pc1``, ``pc2``,
+    ``flow_label`` and ``gt_trans`` are rewritten (contiguous float32 tensors), everything else -- features, masks, interval, pixel
+    measurements, counts -- is invariant and stays.  Padded positions of a ragged batch are transformed like any other.
+    Slot s's transform depends on (seed, aug_draw, slot0 + s) only: Philox4x32-10 keyed by (seed, aug_draw), counter
+    (slot0 + s, 2, 0, 0) -- a stream the sampling of ``draw`` never touches, so ``aug_draw`` may be the draw id itself.
+    ``t_camera_radar``: the shared (4,4) radar-to-camera transform the loss object holds (default ``synth.T_CAMERA_RADAR``, as
+    TrainStep's); a tensor on the batch's device is used as it is, anything else is copied there.
+    Adds ``batch["aug"]`` (B,4,4), the slot's transform, and ``batch["t_camera_radar"]`` (B,4,4), the slot's calibration, which
+    ``TrainStep`` hands to ``RadarFlowLoss``; returns the batch.  CPU tensors raise: there is no fallback."""
+    from . import _lib
+    if not isinstance(augment, Augment):
+        raise TypeError("augment_batch: augment is a dataset.Augment (got %s)" % type(augment).__name__)
+    pc1, pc2, fl, gt = (batch[k] for k in ("pc1", "pc2", "flow_label", "gt_trans"))
+    if not pc1.is_cuda:
+        raise RuntimeError("augment_batch: the batch is on %s; batches are augmented on the GPU only (no CPU fallback)" % pc1.device)
+    if pc1.dim() != 3 or pc2.dim() != 3 or pc1.shape[1] != 3 or pc2.shape[:2] != pc1.shape[:2] or \
+            fl.shape != (pc1.shape[0], pc1.shape[2], 3) or gt.shape != (pc1.shape[0], 4, 4):
+        raise ValueError("augment_batch: pc1 (B,3,N1), pc2 (B,3,N2), flow_label (B,N1,3), gt_trans (B,4,4)")
+    B, _, N1 = pc1.shape
+    N2 = pc2.shape[2]
+    dev = pc1.device
+    tcr = synth.T_CAMERA_RADAR if t_camera_radar is None else t_camera_radar
+    tcr = torch.as_tensor(tcr, dtype=torch.float32).to(dev).contiguous()
+    if tcr.shape != (4, 4):
+        raise ValueError("augment_batch: t_camera_radar is the shared (4,4) matrix")
+    aug = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    calib = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    fp = lambda t: _lib.dev_ptr(t, torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().cmf_augment_batch(
+            int(slot0), B, N1, N2, int(seed) & _MASK64, int(aug_draw) & _MASK64, augment.tan_half_max, int(augment.mirror), fp(tcr),
+            fp(pc1), fp(pc2), fp(fl), fp(gt), fp(aug), fp(calib), _lib.stream_ptr()), "cmf_augment_batch")
+    batch["aug"], batch["t_camera_radar"] = aug, calib
+    return batch
+
+
 DRAW_MAX_POINTS = 16384          # CMF_DRAW_MAX_POINTS of include/cmflow_hip.h: the per-frame cap of cmf_draw_batch (sort keys in LDS)
 _MASK64 = (1 << 64) - 1
 
@@ -394,12 +466,20 @@ class DeviceSplit:
 
     shard_batches = staticmethod(shard_batches)
 
-    def draw(self, frames, npoints, seed, draw, slot0=0):
+    def _calibration(self, t_camera_radar):
+        """The shared radar-to-camera matrix of an augmented iterator on the split's device: copied once per iterator, not per step."""
+        t = synth.T_CAMERA_RADAR if t_camera_radar is None else t_camera_radar
+        return torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous()
+
+    def draw(self, frames, npoints, seed, draw, slot0=0, augment=None, aug_draw=None, t_camera_radar=None):
         """One batch: slot s holds frame ``frames[s]`` resampled to ``npoints`` as ``dataset._resample`` does (n < npoints: all n
         points in order, then uniform duplicates; n >= npoints: a uniformly random subset in uniformly random order), generator
         Philox4x32-10 keyed by (seed, draw) -- a slot's result depends on (seed, draw, slot, frame) only.  ``slot0``: the batch is
         slots ``slot0 .. slot0 + B - 1`` of a larger (global) one -- row s is then, bit for bit, row ``slot0 + s`` of the draw of
         that whole batch, which is how a data-parallel rank draws its share (``cmf_draw_batch_at``).
+        ``augment`` (a ``dataset.Augment``; None: off, nothing more is launched): the drawn batch goes through
+        ``augment_batch(batch, augment, seed, aug_draw, slot0, t_camera_radar)`` -- ``aug_draw`` defaults to ``draw`` -- and gains
+        ``aug`` and ``t_camera_radar``; bit for bit what the two calls give one after the other.
         -> the dict of as_batch_dict plus ``idx1``, ``idx2`` (B, npoints) int32, the drawn point of every position."""
         from . import _lib
         if not self.tab1.is_cuda:
@@ -417,6 +497,8 @@ class DeviceSplit:
                 int(slot0), B, N, len(self), self.max_points, fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans),
                 fp(self.interval), ip(frames), int(seed) & _MASK64, int(draw) & _MASK64, *(fp(out[k]) for k in self.KEYS),
                 ip(out["idx1"]), ip(out["idx2"]), _lib.stream_ptr()), "cmf_draw_batch_at")
+        if augment is not None:
+            augment_batch(out, augment, seed, draw if aug_draw is None else aug_draw, slot0, t_camera_radar)
         return out
 
     def _order(self, count, seed, epoch):
@@ -432,28 +514,36 @@ class DeviceSplit:
                              "of steps and the frames that do not fill a global batch are dropped" % (what, world))
         return rank, world
 
-    def epoch(self, batch_size, npoints, seed, epoch, drop_last=True, rank=0, world=1):
+    def epoch(self, batch_size, npoints, seed, epoch, drop_last=True, rank=0, world=1, augment=None, t_camera_radar=None):
         """One pass over the frames in an order shuffled on the device (torch.randperm, generator seeded by (seed, epoch)): yields
         one batch dict per step; ``draw`` = epoch * steps_per_epoch + step.
         Data parallel (``rank`` of ``world`` processes, ``batch_size`` per rank): the order is the same on every rank, a step is the
         global batch of ``G = world * batch_size`` frames, ``steps = F // G``, and rank r draws rows ``r * batch_size ..`` of it with
         ``slot0 = r * batch_size`` -- the ranks' batches concatenated are, bit for bit, the batches of ``epoch(G, ...)`` in one
-        process, whatever ``world`` is.  ``drop_last=False`` is refused at world > 1 (ValueError)."""
+        process, whatever ``world`` is.  ``drop_last=False`` is refused at world > 1 (ValueError).
+        ``augment`` (a ``dataset.Augment``; None: off): every batch is augmented (``augment_batch``) with ``aug_draw`` = the step's
+        draw id and the rank's ``slot0``, so the ranks' batches still concatenate to the single-process batch.  ``t_camera_radar``:
+        the shared matrix of the loss object the batches go to (default ``synth.T_CAMERA_RADAR``, TrainStep's default)."""
         rank, world = self._equal_steps("DeviceSplit.epoch", rank, world, drop_last)
+        tcr = self._calibration(t_camera_radar) if augment is not None else None
         F, G, at = len(self), world * batch_size, rank * batch_size
         steps = F // G if drop_last else -(-F // G)
         order = self._order(F, seed, epoch).to(torch.int32)
         for step in range(steps):
-            yield self.draw(order[step * G + at:step * G + at + batch_size], npoints, seed, epoch * steps + step, at)
+            yield self.draw(order[step * G + at:step * G + at + batch_size], npoints, seed, epoch * steps + step, at, augment, None, tcr)
 
-    def epoch_clips(self, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1):
+    def epoch_clips(self, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1, augment=None, t_camera_radar=None):
         """CMFlow-T: mini-clips cut as vodClipDataset cuts them (floor(len / L) per clip, remainder dropped), their order
         shuffled; every step yields a list of L batch dicts -- frame j of every mini-clip of the batch -- which TrainStep takes
         frame by frame between reset_clip() calls.  The last step holds the mini-clips left over (fewer than batch_size).
         Data parallel (``rank`` of ``world``, ``batch_size`` per rank): as in ``epoch`` -- the same shuffled starts on every rank,
         global batches of ``world * batch_size`` mini-clips, rank r's rows drawn with ``slot0 = r * batch_size``; at world > 1 the
-        mini-clips that do not fill a global batch are dropped (equal steps on every rank), at world = 1 the short last step stays."""
+        mini-clips that do not fill a global batch are dropped (equal steps on every rank), at world = 1 the short last step stays.
+        ``augment`` / ``t_camera_radar`` as in ``epoch``, with ``aug_draw = epoch * steps + step`` for ALL L frames of a step: a
+        mini-clip keeps ONE transform across its frames (their ``aug`` are equal), because CMFlow-T's recurrent feature is carried
+        from frame to frame and must see one scene."""
         rank, world = _rank_of("DeviceSplit.epoch_clips", rank, world)
+        tcr = self._calibration(t_camera_radar) if augment is not None else None
         if self.clips is None:
             raise ValueError("DeviceSplit.epoch_clips: no clip ranges (build the split with from_dataset on a vodClipDataset)")
         L = int(mini_clip_len)
@@ -465,7 +555,7 @@ class DeviceSplit:
         steps = first.numel() // G if world > 1 else -(-first.numel() // G)
         for step in range(steps):
             f0 = first[step * G + at:step * G + at + batch_size]
-            yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j, at) for j in range(L)]
+            yield [self.draw(f0 + j, npoints, seed, (epoch * steps + step) * L + j, at, augment, epoch * steps + step, tcr) for j in range(L)]
 
     def _ids_to_device(self, ids):
         """A host list of frame ids as an int32 device tensor: one asynchronous copy from pinned memory (the host does not wait)."""
@@ -543,7 +633,7 @@ class DeviceSplit:
         if not self.tab1.is_cuda:
             raise RuntimeError("DeviceSplit.%s: the split is on %s; batches are drawn on the GPU only (no CPU fallback)" % (what, self.device))
 
-    def draw_frames(self, frames, nmax1=None, nmax2=None):
+    def draw_frames(self, frames, nmax1=None, nmax2=None, augment=None, seed=None, aug_draw=None, slot0=0, t_camera_radar=None):
         """One ragged batch of WHOLE frames: slot s holds frame ``frames[s]``, cloud 1 (and everything indexed by its points) padded
         to ``nmax1``, cloud 2 to ``nmax2`` with the frame's first point -- bit for bit what
         as_batch_dict_ragged(extract_data_info_ragged(collate_ragged(items))) gives for the same frames when the two sizes are the
@@ -551,9 +641,14 @@ class DeviceSplit:
         given size smaller than one of the frames raises ValueError.  ``frames`` a device tensor: nothing is read back (but
         counts_host, once per split, when a size is left out); the sizes default to the split-wide maxima per cloud, and a frame
         larger than a given size is truncated (``n1`` / ``n2`` say so).  Ids outside the split are clamped to its first / last frame.
+        ``augment`` (a ``dataset.Augment``; None: off, nothing more is launched): the batch goes through
+        ``augment_batch(batch, augment, seed, aug_draw, slot0, t_camera_radar)`` -- nothing is sampled here, so ``seed`` and ``aug_draw``
+        must then be given (ValueError) -- and gains ``aug`` and ``t_camera_radar``.
         -> the dict of as_batch_dict_ragged plus ``frames`` (B,) int32 on the device, the (clamped) frame of every slot."""
         from . import _lib
         self._need_gpu("draw_frames")
+        if augment is not None and (seed is None or aug_draw is None):
+            raise ValueError("DeviceSplit.draw_frames: augment needs seed and aug_draw (whole frames are not sampled: there is no draw id)")
         on_device = torch.is_tensor(frames) and frames.is_cuda
         # Errors: a size given on the host that is too small for a frame known on the host is this function's ValueError; B = 0
         # and a size outside [1, CMF_DRAW_MAX_NPOINTS] are left to the entry point (its argument error -> RuntimeError), so that
@@ -587,31 +682,39 @@ class DeviceSplit:
             _lib.check(_lib.lib().cmf_draw_frames(
                 B, N1, N2, len(self), fp(self.tab1), fp(self.tab2), ip(self.off1), ip(self.off2), fp(self.trans), fp(self.interval),
                 ip(frames), *(fp(out[k]) for k in self.KEYS), ip(out["n1"]), ip(out["n2"]), _lib.stream_ptr()), "cmf_draw_frames")
+        if augment is not None:
+            augment_batch(out, augment, seed, aug_draw, slot0, t_camera_radar)
         return out
 
-    def draw_frame_batches(self, batches):
+    def draw_frame_batches(self, batches, augment=None, seed=None, aug_draw0=0, slot0=None, t_camera_radar=None):
         """``draw_frames`` for a list of frame-id lists known in advance (an epoch, a sweep, a schedule): all ids go to the device
         here, in ONE asynchronous copy from pinned memory; every batch is then a slice of that tensor with its sizes -- the batch
         maxima -- taken from counts_host, so a step costs launches only and the host never waits for the stream.  An iterator of
-        the batch dicts of ``draw_frames``, bit for bit what ``draw_frames(batch)`` returns for each list."""
+        the batch dicts of ``draw_frames``, bit for bit what ``draw_frames(batch)`` returns for each list.
+        ``augment`` (with ``seed``): batch k is augmented with ``aug_draw = aug_draw0 + k`` and ``slot0[k]`` (a list; None: zeros)."""
         self._need_gpu("draw_frame_batches")
+        if augment is not None and seed is None:
+            raise ValueError("DeviceSplit.draw_frame_batches: augment needs a seed")
         batches = [[int(f) for f in b] for b in batches]
         flat = np.clip(np.array([f for b in batches for f in b], dtype=np.int64), 0, len(self) - 1)
         ids = torch.from_numpy(flat.astype(np.int32)).pin_memory().to(self.device, non_blocking=True) if flat.size else None
-        return self._draw_frame_batches(batches, flat, ids)
+        tcr = self._calibration(t_camera_radar) if augment is not None else None
+        return self._draw_frame_batches(batches, flat, ids, (augment, seed, int(aug_draw0), slot0, tcr))
 
-    def _draw_frame_batches(self, batches, flat, ids):
+    def _draw_frame_batches(self, batches, flat, ids, aug):
         c1, c2 = self.counts_host
+        augment, seed, aug_draw0, slot0, tcr = aug
         first = 0
-        for b in batches:
+        for k, b in enumerate(batches):
             own = flat[first:first + len(b)]
             if len(b):
-                yield self.draw_frames(ids[first:first + len(b)], int(c1[own].max()), int(c2[own].max()))
+                yield self.draw_frames(ids[first:first + len(b)], int(c1[own].max()), int(c2[own].max()), augment, seed, aug_draw0 + k,
+                                       0 if slot0 is None else int(slot0[k]), tcr)
             else:
                 yield self.draw_frames(b)                              # the entry point's argument error
             first += len(b)
 
-    def epoch_ragged(self, batch_size, seed, epoch, bucket=1, drop_last=True, rank=0, world=1):
+    def epoch_ragged(self, batch_size, seed, epoch, bucket=1, drop_last=True, rank=0, world=1, augment=None, t_camera_radar=None):
         """One pass over the whole frames in the shuffled order of ``epoch`` (``_order``, seeded by (seed, epoch); brought to the host
         once), cut by ``ragged_batches`` (``bucket`` > 1: size bucketing inside windows of bucket * batch_size frames) and sent back
         once (``draw_frame_batches``): an iterator of the batch dicts of ``draw_frames``, which TrainStep.step_ragged takes as they
@@ -620,12 +723,14 @@ class DeviceSplit:
         ``world * batch_size`` frames from the order every rank shares, and rank r takes its contiguous slice of each
         (``shard_batches``); ``drop_last=False`` is refused at world > 1 as in ``epoch``.  ``bucket`` > 1 sorts a window by size before
         it is cut, which narrows the size band of a global batch, so the ranks' ``Nmax`` -- and with them their step times --
-        are close; nothing else balances the ranks."""
+        are close; nothing else balances the ranks.
+        ``augment`` / ``t_camera_radar`` as in ``epoch``: step k of the epoch's ``steps`` global batches is augmented with
+        ``aug_draw = epoch * steps + k`` -- the step's draw id -- and ``slot0`` = the position of the rank's slice in the global batch."""
         rank, world = self._equal_steps("DeviceSplit.epoch_ragged", rank, world, drop_last)
         self._need_gpu("epoch_ragged")
-        return self.draw_frame_batches(shard_batches(
-            ragged_batches(self.counts_host[0], self._order(len(self), seed, epoch).tolist(), world * batch_size, bucket, drop_last),
-            rank, world))
+        whole = ragged_batches(self.counts_host[0], self._order(len(self), seed, epoch).tolist(), world * batch_size, bucket, drop_last)
+        slot0 = [rank * (len(b) // world) + min(rank, len(b) % world) for b in whole]       # shard_batches' first row
+        return self.draw_frame_batches(shard_batches(whole, rank, world), augment, seed, int(epoch) * len(whole), slot0, t_camera_radar)
 
     def sweep(self, batch_size, sort_by_size=False, rank=0, world=1):
         """Every frame once, no randomness -- the evaluation iterator: in frame order, or sorted by (n1, frame id) so that a batch

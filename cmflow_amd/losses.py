@@ -86,6 +86,8 @@ def _call_loss(ctx, d, name, size_name, sizes, outs, pred_f, pre_trans, mseg_pre
         d.dyn_mask, d.radar_u, d.radar_v = t["dyn_mask"].data_ptr(), t["radar_u"].data_ptr(), t["radar_v"].data_ptr()
         d.opt, d.pre_trans, d.gt_trans = t["opt"].data_ptr(), pre_trans.data_ptr(), t["gt_trans"].data_ptr()
         d.camera_inverse, d.t_camera_radar = t["camera_inverse"].data_ptr(), t["t_camera_radar"].data_ptr()
+        if "t_camera_radar_batch" in t:                      # a calibration per sample (dataset.augment_batch); else NULL: the shared one
+            d.t_camera_radar_batch = t["t_camera_radar_batch"].data_ptr()
     d.w_self, d.w_em, d.w_ms, d.w_opt, d.w_dyn = hyper["w"]
     d.zeta, d.alpha, d.num_nb, d.lower_bound = hyper["zeta"], hyper["alpha"], hyper["num_nb"], hyper["lower_bound"]
     for field, out in outs.items():
@@ -187,18 +189,22 @@ class RadarFlowLoss(Module):
                                % (NUM_NB, MAX_N, N, self.num_nb))
 
     def forward(self, pc1, pc2, pred_f, vel1, gt_f=None, pre_trans=None, mseg_pre=None, gt_trans=None, mseg_gt=None,
-                dyn_mask=None, radar_u=None, radar_v=None, opt=None):
+                dyn_mask=None, radar_u=None, radar_v=None, opt=None, t_camera_radar=None):
         """With only (pc1, pc2, pred_f, vel1) this is the loss of model 'raflow' (radar_loss.py:274-276): the three
-        self-supervised terms; items then has the four keys of SelfSupervisedLoss (:153-158)."""
+        self-supervised terms; items then has the four keys of SelfSupervisedLoss (:153-158).
+        ``t_camera_radar`` (B,4,4), optional: a radar-to-camera transform per sample -- the optical-flow term of sample i projects
+        through row i instead of the module's shared matrix (an augmented batch's ``batch["t_camera_radar"]``).  None: the shared
+        one, exactly as before."""
         self._check(pc1)
-        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt)
+        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt, t_camera_radar)
         if gt_f is None:
             pre_trans = mseg_pre = None
         total, items = RadarFlowLossFn.apply(pred_f, pre_trans, mseg_pre, data, hyper)
         return total, {k: items[i + 1] for i, k in enumerate(keys)}
 
-    def _data_hyper(self, pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt):
-        """-> the Functions' data and hyper dictionaries and the keys of the reported items; without gt_f the self-only case"""
+    def _data_hyper(self, pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt, t_camera_radar=None):
+        """-> the Functions' data and hyper dictionaries and the keys of the reported items; without gt_f the self-only case (which
+        has no camera term and ignores a per-sample calibration)"""
         if gt_f is None:
             return dict(pc1=pc1, pc2=pc2, vel1=vel1), dict(
                 w=(self.w_self, 0.0, 0.0, 0.0, 0.0), zeta=self.zeta, alpha=self.alpha, num_nb=self.num_nb, lower_bound=0.0,
@@ -206,6 +212,10 @@ class RadarFlowLoss(Module):
         data = dict(pc1=pc1, pc2=pc2, gt_f=gt_f, vel1=vel1, gt_trans=gt_trans, mseg_gt=mseg_gt.to(pc1.dtype),
                     dyn_mask=dyn_mask.to(pc1.dtype), radar_u=radar_u, radar_v=radar_v, opt=opt,
                     camera_inverse=self.camera_inverse, t_camera_radar=self.t_camera_radar)
+        if t_camera_radar is not None:
+            if t_camera_radar.shape != (pc1.shape[0], 4, 4):
+                raise ValueError("RadarFlowLoss: t_camera_radar is (B,4,4), one matrix per sample (got %s)" % (tuple(t_camera_radar.shape),))
+            data["t_camera_radar_batch"] = t_camera_radar
         hyper = dict(w=(self.w_self, self.w_em, self.w_ms, self.w_opt, self.w_dyn), zeta=self.zeta, alpha=self.alpha,
                      num_nb=self.num_nb, lower_bound=self.lower_bound, tiled=self.tiled)
         return data, hyper, ITEM_KEYS
@@ -235,7 +245,7 @@ class RadarFlowLoss(Module):
             raise RuntimeError("cmflow_amd.losses.RadarFlowLoss runs on the GPU only (got %s tensors)" % pc1.device)
 
     def forward_ragged(self, pc1, pc2, pred_f, vel1, npoints1, npoints2, gt_f=None, pre_trans=None, mseg_pre=None, gt_trans=None,
-                       mseg_gt=None, dyn_mask=None, radar_u=None, radar_v=None, opt=None, validate=False):
+                       mseg_gt=None, dyn_mask=None, radar_u=None, radar_v=None, opt=None, validate=False, t_camera_radar=None):
         """The loss of B whole frames of their own sizes in one call (cmf_radar_loss_counted).  pc1, pred_f, gt_f (B,3,Nmax1), pc2
         (B,3,Nmax2), per-point tensors of cloud 1 (B,Nmax1[,2]) padded; npoints1, npoints2 (B,) int32 on the device,
         num_nb < npoints1[i] <= Nmax1, 1 <= npoints2[i] <= Nmax2.
@@ -245,9 +255,10 @@ class RadarFlowLoss(Module):
         total is differentiable w.r.t. pred_f, pre_trans, mseg_pre; padded slots of the gradients are 0.  Padded input slots must
         be finite and influence nothing.  validate=True checks the counts on the host (ValueError; a device -> host sync), otherwise
         they are trusted: the kernels clamp them to [num_nb + 1, Nmax1] / [1, Nmax2], so a wrong count gives wrong numbers, not a
-        wild access.  Without gt_f: the three self-supervised terms (model 'raflow'), as in ``forward``."""
+        wild access.  Without gt_f: the three self-supervised terms (model 'raflow'), as in ``forward``.  ``t_camera_radar`` (B,4,4):
+        a calibration per sample, as in ``forward``."""
         self._check_ragged(pc1, pc2, pred_f, npoints1, npoints2, validate)
-        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt)
+        data, hyper, keys = self._data_hyper(pc1, pc2, vel1, gt_f, gt_trans, mseg_gt, dyn_mask, radar_u, radar_v, opt, t_camera_radar)
         if gt_f is None:
             pre_trans = mseg_pre = None
         total, items, per_sample = RadarFlowLossRaggedFn.apply(pred_f, pre_trans, mseg_pre, dict(data, n1=npoints1, n2=npoints2), hyper)

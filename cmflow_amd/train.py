@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import synth
+from .dataset import Augment
 from .dp import FlatAdam, FlatGradBucket, SegmentedReducer, ema_options, guard_options
 from .fused_blocks import join_side_streams
 from .losses import RadarFlowLoss, make_labels, make_labels_ragged
@@ -84,6 +85,9 @@ class TrainStep:
         self.gfeat = None
 
     def forward_loss(self, batch):
+        """``batch["t_camera_radar"]`` (B,4,4), when present -- an augmented batch (dataset.augment_batch) -- is the calibration per
+        sample the loss projects through; it must have been derived from this step's ``loss_obj.t_camera_radar`` (the iterators'
+        ``t_camera_radar`` argument; ``train_epoch`` / ``train_epoch_clips`` pass it)."""
         pc1, pc2, ft1, ft2 = batch["pc1"], batch["pc2"], batch["ft1"], batch["ft2"]
         if self.self_supervised:                                   # model 'raflow': main_util.py:57-60
             output, pred_f, pre_trans, mask_s = self.net(pc1, pc2, ft1, ft2, batch["interval"])
@@ -97,7 +101,7 @@ class TrainStep:
             pred_f, mseg_pre, pre_trans, mask = self.net(pc1, pc2, ft1, ft2, mseg_gt, 'train')
         loss, items = self.loss_obj(pc1, pc2, pred_f, ft1[:, 0], batch["flow_label"].transpose(2, 1), pre_trans,
                                     mseg_pre, batch["gt_trans"], mseg_gt, dyn_mask, batch["radar_u"],
-                                    batch["radar_v"], batch["opt_flow"])
+                                    batch["radar_v"], batch["opt_flow"], t_camera_radar=batch.get("t_camera_radar"))
         return loss, items, (pred_f, mseg_pre, pre_trans, mask), (dyn_mask, mseg_gt)
 
     def _segment_ready(self, i):
@@ -148,7 +152,8 @@ class TrainStep:
             pred_f, mseg_pre, pre_trans, mask = self.net.forward_ragged_train(pc1, pc2, ft1, ft2, n1, n2, mseg_gt, validate=validate)
         loss, items, per_sample = self.loss_obj.forward_ragged(pc1, pc2, pred_f, ft1[:, 0], n1, n2, batch["flow_label"].transpose(2, 1),
                                                                pre_trans, mseg_pre, batch["gt_trans"], mseg_gt, dyn_mask,
-                                                               batch["radar_u"], batch["radar_v"], batch["opt_flow"], validate=validate)
+                                                               batch["radar_u"], batch["radar_v"], batch["opt_flow"], validate=validate,
+                                                               t_camera_radar=batch.get("t_camera_radar"))
         items = dict(items, per_sample=per_sample)
         return loss, items, (pred_f, mseg_pre, pre_trans, mask), (dyn_mask, mseg_gt)
 
@@ -185,7 +190,7 @@ def _count(n, dev):
     return torch.full((), float(n), dtype=torch.float64, device=dev)
 
 
-def train_epoch(step, split, batch_size, npoints, seed, epoch, rank=0, world=1):
+def train_epoch(step, split, batch_size, npoints, seed, epoch, rank=0, world=1, augment=None):
     """train_one_epoch (main_util.py:39-90) for CMFlow / RaFlow: ``step`` (a TrainStep) on every batch of
     ``split.epoch(batch_size, npoints, seed, epoch, drop_last=True, rank, world)`` -- the reference's shuffled loader with drop_last
     (main.py:207).  -> (total_loss, loss_items): ``total_loss = sum loss * B / sum B`` and, per key of the step's items, the mean
@@ -193,9 +198,11 @@ def train_epoch(step, split, batch_size, npoints, seed, epoch, rank=0, world=1):
     here they are taken in step order, which is numpy's order below 8 steps and differs from its pairwise order in the last
     bits above).  Inside the loop the host only enqueues: nothing is read back, so it never waits for the device.
     Like the reference it does NOT touch ``net.training``: whoever called ``net.eval()`` last decides the BatchNorm regime (``fit``).
-    At world > 1 the statistics are this rank's own (``fit`` averages them over the ranks once per epoch)."""
+    At world > 1 the statistics are this rank's own (``fit`` averages them over the ranks once per epoch).
+    ``augment`` (a ``dataset.Augment``; None: off) goes to ``split.epoch`` together with the step's own shared calibration
+    (``step.loss_obj.t_camera_radar``), from which every batch's per-sample calibration is derived."""
     rows, weights = [], []
-    for batch in split.epoch(batch_size, npoints, seed, epoch, True, rank, world):
+    for batch in split.epoch(batch_size, npoints, seed, epoch, True, rank, world, augment, _calibration_of(step, augment)):
         loss, items = step(batch)[:2]
         rows.append(torch.stack([loss, *items.values()]))
         weights.append(int(batch["pc1"].shape[0]))
@@ -204,17 +211,23 @@ def train_epoch(step, split, batch_size, npoints, seed, epoch, rank=0, world=1):
     return total, {k: means[i] for i, k in enumerate(keys)}
 
 
-def train_epoch_clips(step, split, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1):
+def _calibration_of(step, augment):
+    """The shared radar-to-camera matrix an augmented iterator starts from: the one the step's loss object holds."""
+    return step.loss_obj.t_camera_radar if augment is not None else None
+
+
+def train_epoch_clips(step, split, batch_size, mini_clip_len, npoints, seed, epoch, rank=0, world=1, augment=None):
     """train_one_epoch_seq (clip_util.py:20-78) for CMFlow_T over ``split.epoch_clips(...)``: ``net.train()`` at entry (:25 -- unlike
     train_one_epoch, so CMFlow-T trains every epoch under train-mode BatchNorm), then per step ``step.reset_clip()`` and one
     optimizer step per frame of the mini-clips, the recurrent state carried (detached) from frame to frame.  A step's loss is the
     float32 mean over its L frames (:64,68), its items the float64 means over the frames (:70); ``total_loss`` weights the steps by
     their number of mini-clips (the last step of ``epoch_clips`` may be short at world = 1) and the items are averaged over the
-    steps (:71-76).  Returns and the no-read-back rule as in train_epoch."""
+    steps (:71-76).  Returns and the no-read-back rule as in train_epoch.  ``augment`` as in train_epoch: a mini-clip keeps one
+    transform across its frames (``DeviceSplit.epoch_clips``)."""
     step.net.train()
     L = int(mini_clip_len)
     rows, weights = [], []
-    for clip in split.epoch_clips(batch_size, L, npoints, seed, epoch, rank, world):
+    for clip in split.epoch_clips(batch_size, L, npoints, seed, epoch, rank, world, augment, _calibration_of(step, augment)):
         step.reset_clip()
         frames = []
         for batch in clip:
@@ -268,6 +281,19 @@ def _broadcast_buffers(net, group):
         dist.broadcast(t.data, src=src, group=group)
 
 
+OPTIONAL_SETTINGS = {"max_grad_norm": None, "skip_nonfinite": False, "ema_decay": None, "augment": None}
+
+
+def check_resume_settings(stored, given):
+    """fit's comparison of a resume point's settings with the call's: every setting of the call must equal the stored one, where
+    the options a run only records when they are on (OPTIONAL_SETTINGS: the guard, the average, the augmentation) count as off on
+    the side that lacks them.  A difference raises ValueError naming (stored, given) per key."""
+    stored, given = dict(OPTIONAL_SETTINGS, **stored), dict(OPTIONAL_SETTINGS, **given)
+    differ = {k: (stored.get(k), v) for k, v in given.items() if stored.get(k) != v}
+    if differ:
+        raise ValueError("fit: the resume point was written by a run with other settings (stored, given): %s" % differ)
+
+
 def _refuse(net, train_split, val_split, epochs, rank, world, group):
     """fit's refusals, before anything is launched, built or switched."""
     from .cmflow import CMFlow_T
@@ -287,7 +313,7 @@ def _refuse(net, train_split, val_split, epochs, rank, world, group):
 
 def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_points, lr=1e-3, decay_epochs=1, decay_rate=0.9,
         seed=1234, mini_clip_len=5, vr_thres=0.3, out_dir=None, resume=None, on_epoch=None, rank=0, world=1, group=None, args=None,
-        max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+        max_grad_norm=None, skip_nonfinite=False, ema_decay=None, augment=None):
     """The reference's ``train()`` (main.py:104-170) on two device-resident splits, without its plots and log files; the defaults
     are configs.yaml's.  One TrainStep (Adam, weight decay 1e-4) and one StepLR (``make_schedule``), then per epoch:
 
@@ -346,7 +372,16 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     exchanged for it -- every rank's parameters are bit-identical (one averaged gradient), so every rank's ``ema`` is; each rank
     swaps its own copy in for the validation and rank 0 writes.
 
-    Refused before anything is launched and before any mode changes: a bad ``max_grad_norm`` or ``ema_decay`` (ValueError), ``epochs < 1``, CMFlow_T with a split without clip ranges, a
+    Augmentation.  ``augment`` (a ``dataset.Augment``; None: off) goes to the TRAINING iterator only (``train_epoch`` /
+    ``train_epoch_clips``): every training batch is rotated about the sensor's z axis and, optionally, mirrored, slot by slot, with
+    its labels and calibration (``dataset.augment_batch``; one small launch more per step); the validation sweeps are never
+    augmented.  The transforms depend on (seed, epoch, step, slot) only, so a resumed run continues bit for bit.  The settings gain
+    ``augment`` -- the plain tuple ``(yaw_deg, mirror)`` -- only when it is on; a resume point without it compares as "off" and a
+    mismatch either way raises ValueError.  With ``augment=None`` settings and launches are exactly what they were.  Tested: the
+    labels' consistency and the loss's invariance; not claimed: any effect on accuracy.
+
+    Refused before anything is launched and before any mode changes: a bad ``max_grad_norm`` or ``ema_decay`` (ValueError), an
+    ``augment`` that is not a ``dataset.Augment`` (TypeError), ``epochs < 1``, CMFlow_T with a split without clip ranges, a
     bad rank / world, ``world > 1`` without an initialised process group (ValueError); a model that is not CMFlow / CMFlow_T /
     RaFlow (NotImplementedError); a split or a network that is not on the GPU (RuntimeError).
     Whole-frame training (``epoch_ragged`` / ``step_ragged``) is not driven from here: its epoch 0 would need train-mode BatchNorm
@@ -355,6 +390,8 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     max_grad_norm, skip_nonfinite = guard_options(max_grad_norm, skip_nonfinite)
     guarded = max_grad_norm is not None or skip_nonfinite
     ema_decay = ema_options(ema_decay)
+    if augment is not None and not isinstance(augment, Augment):
+        raise TypeError("fit: augment is a dataset.Augment or None (got %s)" % type(augment).__name__)
     recurrent, rank, world = _refuse(net, train_split, val_split, epochs, rank, world, group)
     dev = train_split.device
     settings = {"model": type(net).__name__, "batch_size": int(batch_size), "val_batch_size": int(val_batch_size),
@@ -365,16 +402,14 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
         settings.update(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     if ema_decay is not None:
         settings.update(ema_decay=ema_decay)
+    if augment is not None:
+        settings.update(augment=tuple(augment))
     state = None
     if resume is not None:
         state = torch.load(resume, map_location=dev)
         if not isinstance(state, dict) or state.get("format") != "cmflow_amd.fit" or state.get("version") != RESUME_VERSION:
             raise ValueError("fit: %s is not a resume point of format version %d" % (resume, RESUME_VERSION))
-        off = {"max_grad_norm": None, "skip_nonfinite": False, "ema_decay": None}    # a resume point without them: guard / average off
-        stored, given = dict(off, **state["settings"]), dict(off, **settings)
-        differ = {k: (stored.get(k), v) for k, v in given.items() if stored.get(k) != v}
-        if differ:
-            raise ValueError("fit: the resume point was written by a run with other settings (stored, given): %s" % differ)
+        check_resume_settings(state["settings"], settings)
     step = TrainStep(net, vr_thres=vr_thres, lr=lr, group=group, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
                      ema_decay=ema_decay)
     scheduler = make_schedule(step.opt, decay_epochs, decay_rate)
@@ -394,9 +429,9 @@ def fit(net, train_split, val_split, *, epochs, batch_size, val_batch_size, num_
     for epoch in range(first, int(epochs)):
         rate = step.opt.param_groups[0]["lr"]
         if recurrent:
-            total, items = train_epoch_clips(step, train_split, batch_size, mini_clip_len, num_points, seed, epoch, rank, world)
+            total, items = train_epoch_clips(step, train_split, batch_size, mini_clip_len, num_points, seed, epoch, rank, world, augment)
         else:
-            total, items = train_epoch(step, train_split, batch_size, num_points, seed, epoch, rank, world)
+            total, items = train_epoch(step, train_split, batch_size, num_points, seed, epoch, rank, world, augment)
         if world > 1:
             _broadcast_buffers(net, group)
         with step.opt.ema_weights() if ema_decay is not None else contextlib.nullcontext():      # the averaged model is what is scored

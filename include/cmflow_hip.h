@@ -679,6 +679,9 @@ typedef struct cmf_radar_loss_desc {
     float *items;                                                              /* [9] */
     float *d_pred_f, *d_pre_trans, *d_mseg_pre;                                /* (B,3,N), (B,4,4), (B,N) or NULL */
     float *workspace;                                                          /* cmf_radar_loss_workspace_nb floats */
+    const float *t_camera_radar_batch;   /* (B,4,4) or NULL.  Non-NULL: sample i projects through row i instead of t_camera_radar
+                                            (cmf_augment_batch's calib); NULL: the shared matrix.  Appended last: a caller built
+                                            against the shorter struct must zero-initialise the descriptor */
 } cmf_radar_loss_desc;
 long long cmf_radar_loss_workspace_nb(int b, int n, int num_nb);   /* floats; num_nb as in the descriptor */
 int cmf_radar_loss(const cmf_radar_loss_desc *d, void *stream);
@@ -806,6 +809,7 @@ typedef struct cmf_radar_loss_counted_desc {
     float *items_mean;                                                         /* [9] */
     float *d_pred_f, *d_pre_trans, *d_mseg_pre;                                /* (B,3,N1max), (B,4,4), (B,N1max) or NULL */
     float *workspace;                                                          /* cmf_radar_loss_counted_workspace floats */
+    const float *t_camera_radar_batch;                                         /* (B,4,4) or NULL, as in cmf_radar_loss_desc */
 } cmf_radar_loss_counted_desc;
 long long cmf_radar_loss_counted_workspace(int b, int n1max, int n2max, int num_nb);
 int cmf_radar_loss_counted(const cmf_radar_loss_counted_desc *d, void *stream);
@@ -871,6 +875,48 @@ int cmf_draw_frames(int B, int nmax1, int nmax2, int nframes, const float *tab1,
                     const int *off2, const float *trans, const float *interval, const int *frames,
                     float *pc1, float *pc2, float *ft1, float *ft2, float *gt_trans, float *flow_label, float *fg_mask,
                     float *interval_out, float *radar_u, float *radar_v, float *opt_flow, int *n1, int *n2, void *stream);
+
+/* cmf_augment_batch: one label-consistent transform per slot of an already drawn batch, in place (dataset.augment_batch; DESIGN.md
+ *   section 19) -- a rotation about the sensor's z axis, optionally after a mirror of the y axis.  Both fix the sensor origin, so
+ *   ranges, radial velocities, features, masks, intervals and pixel measurements are untouched; coordinates, flow labels, gt_trans
+ *   and the radar-to-camera transform change covariantly.  A definition, not an approximation of one; tests/augment_ref.py
+ *   restates it in numpy, bit for bit.  One launch, one workgroup per (chunk of 256 positions, slot); dense batches (n1 == n2) and
+ *   ragged ones alike; padded positions are transformed like any other (a ragged batch's padding stays a copy of the first row).
+ *   pc1 (B,3,n1), pc2 (B,3,n2), flow_label (B,n1,3), gt_trans (B,16): in place.  t_camera_radar (16): the shared calibration.
+ *   -> aug (B,16): the slot's transform A as a 4 x 4; calib (B,16): the slot's radar-to-camera transform (cmf_radar_loss_desc's
+ *   t_camera_radar_batch).
+ *   Generator: the key of the call = words 0, 1 of Philox4x32-10 with counter (seed lo, seed hi, aug_draw lo, aug_draw hi) and key
+ *   (0, 0), as in cmf_draw_batch; slot s takes the words of counter (slot0 + s, 2, 0, 0) under that key.  cmf_draw_batch's counters
+ *   have 0 or 1 in that second place, so the two streams never meet, even with aug_draw == draw.  u32 = word 0 decides the angle;
+ *   m = -1 when mirror != 0 and bit 31 of word 1 is set, else m = +1.
+ *   Angle, float64, every operation rounded on its own (no contraction), no trigonometric function:
+ *     r = u32 * 2^-32;   t = ((2 r) - 1) * tan_half_max;   q = t * t;   d = 1 + q;   c = (1 - q) / d;   s = (2 t) / d;
+ *     cf = (float)c;   sf = (float)s.
+ *   The angle is 2 atan(t) with t uniform in [-tan_half_max, tan_half_max): tan_half_max = tan(yaw_max / 2) (the caller's, computed
+ *   once on the host) bounds it by yaw_max, but it is uniform in t and NOT exactly uniform in the angle (its density is
+ *   proportional to 1 + t^2: at yaw_max = 10 degrees it varies by 0.8 %, towards 180 degrees the angles crowd at the two ends).  c * c + s * s = 1 up to float64 rounding,
+ *   cf * cf + sf * sf = 1 up to float32 rounding of the two: A is orthogonal to about 2^-23, not exactly.
+ *   A = [cf, -m sf, 0;  sf, m cf, 0;  0, 0, 1]  (its float32 entries; the products by m = +-1 are exact).
+ *   Points of pc1, pc2 and rows of flow_label, float32, every operation rounded on its own:
+ *     ym = m * y;   x' = (cf * x) - (sf * ym);   y' = (sf * x) + (cf * ym);   z' = z (not touched).
+ *   Transforms, float64 from the float32 entries, every operation rounded on its own, a dot product of three terms is
+ *   (a0 b0 + a1 b1) + a2 b2 with the zeros and ones of A taking part as numbers, each result rounded to float32 once at the end.
+ *   With R, t the upper 3 x 3 and the translation of gt_trans, Rc, tc those of t_camera_radar, and A^-1 := A^T = diag(1, m, 1) Rz^T
+ *   (the transpose of the float32 entries -- the inverse up to the rounding above):
+ *     H = R A^T:  H[i][j] = (R[i][0] A[j][0] + R[i][1] A[j][1]) + R[i][2] A[j][2]        (float64, kept)
+ *     gt_trans':  R'[i][j] = (A[i][0] H[0][j] + A[i][1] H[1][j]) + A[i][2] H[2][j];   t'[i] = (A[i][0] t[0] + A[i][1] t[1]) + A[i][2] t[2]
+ *     calib:      Rc'[i][j] = (Rc[i][0] A[j][0] + Rc[i][1] A[j][1]) + Rc[i][2] A[j][2];   tc' = tc (copied)
+ *     aug:        A in the upper 3 x 3, zero translation.
+ *   The bottom rows of the three are written as exactly (0,0,0,1).
+ *   Exact identity: a slot with cf == 1, sf == 0 (either sign) and m == 1 is not computed but copied -- its points, flow rows and
+ *   gt_trans (all 16 entries) keep their bits (signed zeros and NaN payloads included), aug = I, and the upper three rows of calib are
+ *   those of t_camera_radar bit for bit.
+ *   tan_half_max == 0 with mirror == 0 makes every slot such a slot.
+ *   1 <= B <= 65535, 1 <= n1, n2 <= CMF_DRAW_MAX_NPOINTS, slot0 >= 0, slot0 + B <= INT_MAX, tan_half_max finite and >= 0: an argument
+ *   error otherwise, never an access outside the tensors. */
+int cmf_augment_batch(int slot0, int B, int n1, int n2, unsigned long long seed, unsigned long long aug_draw,
+                      double tan_half_max, int mirror, const float *t_camera_radar, float *pc1, float *pc2, float *flow_label,
+                      float *gt_trans, float *aug, float *calib, void *stream);
 
 /* ---- from raw radar scans to the packed split (cmflow_amd/prepare.py) ----------------------------------------
  * The arithmetic of the reference's offline preprocess step (preprocess/utils/get_flow_samples.py) on batches of scans and pairs.
