@@ -212,6 +212,43 @@ class SplitResults:
                 json.dump(res, fh)
         return paths
 
+    def write_vis(self, directory, split, layers=("flow", "seg_gt"), frames=None, view=None, chunk=64):
+        """The reference's ``--vis`` pictures (main_util.py:170-172): ``directory/<layer>/<global frame index>.png`` for every selected
+        frame and every layer of ``layers`` (``vis.LAYERS``), as ``args.vis_path_flow/{num_pcs}.png`` and
+        ``args.vis_path_seg/{num_pcs}.png`` -- the two default layers are the two pictures the reference writes (its "seg" figure is
+        coloured by the ground-truth mask).  ``frames``: None (all), a list or an int64 tensor (``worst(...)``'s); ``view``: a
+        ``vis.BevView``.  ``vis.render`` draws ``chunk`` frames at a time, ONE device-to-host copy per chunk and layer, so memory stays
+        bounded (2.16 MB per default picture).  Every selected frame must be ``done``, else ValueError (before anything is written).
+        -> the list of paths written: layer by layer, in the order of ``frames``."""
+        from . import vis
+        layers = [layers] if isinstance(layers, str) else list(layers)
+        for layer in layers:
+            vis._layer_id(layer, "SplitResults.write_vis")
+        vis.check_store(self, split, "SplitResults.write_vis")
+        chunk = int(chunk)
+        if not 1 <= chunk <= vis.MAX_FRAMES:
+            raise ValueError("SplitResults.write_vis: chunk = %d" % chunk)
+        F = len(self)
+        ids = np.arange(F, dtype=np.int64) if frames is None else \
+            (frames.detach().cpu().numpy() if torch.is_tensor(frames) else np.asarray(list(frames))).astype(np.int64).reshape(-1)
+        if ids.size and not (0 <= ids.min() and ids.max() < F):
+            raise ValueError("SplitResults.write_vis: frames outside 0 .. %d" % (F - 1))
+        done = self.done.cpu().numpy()
+        if not done[ids].all():
+            raise ValueError("SplitResults.write_vis: %d of the %d selected frames have no results" % (int((done[ids] == 0).sum()), ids.size))
+        paths = []
+        for layer in layers:
+            folder = os.path.join(directory, layer)
+            os.makedirs(folder, exist_ok=True)
+            for a in range(0, ids.size, chunk):
+                part = ids[a:a + chunk]
+                images = vis.render(self, split, layer, None if frames is None and chunk >= F else torch.from_numpy(part), view).cpu().numpy()
+                for f, image in zip(part.tolist(), images):
+                    paths.append(os.path.join(folder, "%d.png" % f))
+                    with open(paths[-1], "wb") as fh:
+                        fh.write(vis.encode_png(image))
+        return paths
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

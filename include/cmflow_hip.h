@@ -1017,6 +1017,56 @@ int cmf_eval_metrics_frames(int b, int n, const int *cnt, const float *pc, const
                             double *workspace, void *stream);
 int cmf_pose_chain(int nframes, int nclips, const float *T, const int *clips, double *poses, void *stream);
 
+/* ---- a test run's results as bird's-eye-view images (cmflow_amd/vis.py) -----------------------------------------
+ * The reference's `--vis` branch (main_util.py:170-172) on the packed store above: per-point colour, then a small rasteriser.  Both
+ * entries take a SELECTION of frames: frames (nsel) int64 in device memory (ids clamped to [0, nframes-1]; the same id may occur
+ * twice), or NULL for frames 0 .. nsel-1.  off1 / total as in cmf_pack_results: a frame whose rows do not lie inside [0, total) is
+ * treated as empty, so a bad id or offset gives a wrong picture, never an access outside the store.
+ *
+ * cmf_vis_point_colors (utils/vis_util.py:32-42,63 and :139-140 with utils/vis_ops.py:3-50,54-91): colors (total,3) and drawn (total)
+ *   bytes, written at the store's own rows for the selected frames and nowhere else.  One wavefront per frame, lane-strided.
+ *   flow (total,3) float32: the store's; tab1: the split's cloud-1 table with ld_tab floats per row (label flow at columns 6..8, mask
+ *   at column 9); mask (total) bytes: the store's.  What a layer does not read may be NULL.  Layers:
+ *     CMF_VIS_FLOW     the predicted flow on the Middlebury wheel: rad_max = max_i sqrt(fx_i^2 + fy_i^2) over the frame (exact in any
+ *                      order), d = rad_max + 1e-5, u = fx / d, v = -(fy / d), and then flow_xy_to_colors(u, v):
+ *                        rad = sqrt(u^2 + v^2);  a = atan2(-v, -u) / pi;  fk = (a + 1) / 2 * 54;  k0 = floor(fk) clamped to [0, 54];
+ *                        k1 = k0 + 1, 55 -> 0;  f = fk - k0;  per channel col = (1 - f) * (w[k0] / 255) + f * (w[k1] / 255);
+ *                        rad <= 1: col = 1 - rad * (1 - col), else col = col * 0.75;  value = floor(255 * col).
+ *                      All in float64 from the float32 inputs, every operation rounded on its own, in this order (the reference takes
+ *                      the angle in float32).  A NaN flow gives an unspecified colour for its frame, never a
+ *                      read outside the 55-entry table.
+ *     CMF_VIS_FLOW_GT  the same with the label flow as (fx, fy) but the PREDICTED flow's d, as vis_util.py:41-42 forms x_gt, y_gt.
+ *     CMF_VIS_SEG      the predicted mask byte: 0 -> (255, 99, 71), otherwise (65, 105, 225).
+ *     CMF_VIS_SEG_GT   the split's mask column: == 0 -> (255, 99, 71), == 1 -> (65, 105, 225), any other value: colour (0, 0, 0)
+ *                      and drawn = 0 (the reference scatters `mask == 0` and `mask == 1` and nothing else).
+ *   drawn is 1 for every point of the other three layers.
+ *
+ * cmf_vis_render_bev (utils/vis_util.py:65-90 and :139-165): out (nsel,height,width,3) bytes, a pure function of the inputs -- no
+ *   atomics, every pixel written once by the thread that owns it.  xyz: the cloud-1 positions with ld_xyz floats per row (the
+ *   split's tab1).  All arithmetic float32, + - * and compares only, nothing contracted:
+ *     pixel (row r, col c) has the centre cx = c + 0.5, cy = r + 0.5; a point sits at pu = (px - x0) * inv_s, pv = (y1 - py) * inv_s
+ *     (row 0 is the largest y) and covers the pixel iff (cx-pu)*(cx-pu) + (cy-pv)*(cy-pv) <= r2.  The pixel takes the colour of the
+ *     HIGHEST-indexed point of the frame with drawn != 0 that covers it (matplotlib paints in order), else (80, 80, 80).  A NaN
+ *     coordinate covers nothing.  guides != 0: a pixel whose centre x = x0 + cx * s, y = y1 - cy * s lies on a guide is white, over
+ *     the points -- range rings r = 10 .. 50: (r-half)^2 <= x*x + y*y <= (r+half)^2, x >= 0, |y| <= 10 (r = 10) or 12.5; bearing
+ *     lines at 0, +-5, +-10, +-15 degrees: |y - t*x| <= half * k, 0 <= x <= 60, (t, k) = (tan, sqrt(1 + tan^2)) from a table of float
+ *     literals.  The reference's text labels are not drawn.
+ *   The host passes s (metres per pixel), inv_s = 1/s, half = s/2, radius (pixels; used only to cull, must satisfy
+ *   r2 <= (radius + 0.5)^2) and r2 as float32.  nsel <= 65535, width, height <= CMF_VIS_MAX_SIDE.
+ *   tests/vis_ref.py restates both entries in numpy, bit for bit. */
+#define CMF_VIS_FLOW 0
+#define CMF_VIS_FLOW_GT 1
+#define CMF_VIS_SEG 2
+#define CMF_VIS_SEG_GT 3
+#define CMF_VIS_MAX_SIDE 4096
+int cmf_vis_point_colors(int nsel, int nframes, const long long *frames, const int *off1, long long total, int layer,
+                         const float *flow, const float *tab1, int ld_tab, const unsigned char *mask,
+                         unsigned char *colors, unsigned char *drawn, void *stream);
+int cmf_vis_render_bev(int nsel, int nframes, const long long *frames, const int *off1, long long total, const float *xyz,
+                       int ld_xyz, const unsigned char *colors, const unsigned char *drawn, int width, int height,
+                       float x0, float y1, float s, float inv_s, float half, float radius, float r2, int guides,
+                       unsigned char *out, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
