@@ -162,6 +162,8 @@ SIGNATURES = {
     # a test run's results as bird's-eye-view images (vis.py)
     "cmf_vis_point_colors": [_ci, _ci, _vp, _vp, _ll, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp],
     "cmf_vis_render_bev": [_ci, _ci, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _cf, _cf, _cf, _ci, _vp, _vp],
+    # a test run's clouds accumulated over a window of frames (accumulate.py)
+    "cmf_accumulate": [_ci, _ci, _vp, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _ll, _vp, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

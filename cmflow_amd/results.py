@@ -249,6 +249,11 @@ class SplitResults:
                         fh.write(vis.encode_png(image))
         return paths
 
+    def accumulate(self, split, window=8, which="pred", dynamic="keep", frames=None):
+        """``accumulate.accumulate(split, self, ...)``: the clouds of ``frames`` accumulated over ``window`` frames of their clip."""
+        from . import accumulate as A
+        return A.accumulate(split, self, window=window, which=which, dynamic=dynamic, frames=frames)
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

@@ -144,6 +144,57 @@ def render(store, split, layer, frames=None, view=None):
     return out
 
 
+AGE_LAYER = "age"                                           # render_accumulated only: royal blue fading into the background with age
+_ROYAL_BLUE, _BACKGROUND = (65, 105, 225), (80, 80, 80)
+
+
+def age_colors(age, window):
+    """The colours of the ``'age'`` layer, (n, 3) uint8 from ages (n) uint8 on any device: channel c of a point of age g is
+    (blue_c * (window - g) + background_c * g) // window in whole numbers -- royal blue (65, 105, 225) for the current scan, one
+    step short of the background (80, 80, 80) for the oldest age a full window has.  Ages from ``window`` on give the background."""
+    window = int(window)
+    g = age.to(torch.int32).clamp(max=window)
+    channels = [torch.div(blue * (window - g) + back * g, window, rounding_mode="floor") for blue, back in zip(_ROYAL_BLUE, _BACKGROUND)]
+    return torch.stack(channels, dim=1).to(torch.uint8)
+
+
+def render_accumulated(acc, store, split, layer, view=None):
+    """Bird's-eye-view pictures of accumulated clouds (``accumulate.accumulate``) -> (len(acc), H, W, 3) uint8 on the device, one
+    picture per target frame.  ``layer``: one of ``LAYERS`` -- every point keeps the colour ``point_colors(store, split, layer)``
+    gives it in its own source frame (the flow wheel is normalised per source frame), gathered by ``acc.src`` -- or ``'age'``
+    (``age_colors``; ``store`` is not read and may be None).  A row behind a target's count (``src < 0``) is not drawn.  Rows run
+    oldest first, so the newest scan is painted on top.  ``view`` as ``render``.  The colour launch, a few gathers and ONE call of the
+    rasteriser ``render`` uses (``cmf_vis_render_bev`` over ``acc.off`` / ``acc.xyz``); the host never waits."""
+    if layer != AGE_LAYER:
+        _layer_id(layer, "vis.render_accumulated")
+        check_store(store, split, "vis.render_accumulated")
+    if not (acc.xyz.is_cuda and acc.xyz.device == split.tab1.device):
+        raise RuntimeError("vis.render_accumulated: clouds on %s, split on %s; pictures are rendered on the GPU only" % (acc.xyz.device, split.tab1.device))
+    view = BevView() if view is None else view
+    nsel, R, u8 = len(acc), acc.xyz.shape[0], torch.uint8
+    if nsel > MAX_FRAMES:
+        raise ValueError("vis.render_accumulated: %d targets in one call (at most %d)" % (nsel, MAX_FRAMES))
+    out = torch.empty((nsel, view.height, view.width, 3), dtype=u8, device=acc.device)
+    if nsel == 0:
+        return out
+    held = acc.src >= 0
+    if layer == AGE_LAYER:
+        colors, drawn = age_colors(acc.age, acc.window), held.to(u8)
+    else:
+        all_colors, all_drawn = point_colors(store, split, layer)
+        row = acc.src.clamp(min=0).long()
+        colors, drawn = all_colors[row], all_drawn[row] * held.to(u8)
+    colors, drawn = colors.contiguous(), drawn.contiguous()
+    p = {k: float(v) for k, v in view.kernel_params().items()}
+    with torch.cuda.device(acc.device):
+        _lib.check(_lib.lib().cmf_vis_render_bev(
+            nsel, nsel, None, _lib.dev_ptr(acc.off, torch.int32), R, _lib.dev_ptr(acc.xyz, torch.float32), 3,
+            _lib.dev_ptr(colors, u8), _lib.dev_ptr(drawn, u8), view.width, view.height,
+            p["x0"], p["y1"], p["s"], p["inv_s"], p["half"], p["radius"], p["r2"], int(view.guides),
+            _lib.dev_ptr(out, u8), _lib.stream_ptr()), "cmf_vis_render_bev")
+    return out
+
+
 # ---- PNG, with the stdlib only ----------------------------------------------------------------------------------------------------------
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
 

@@ -1067,6 +1067,55 @@ int cmf_vis_render_bev(int nsel, int nframes, const long long *frames, const int
                        float x0, float y1, float s, float inv_s, float half, float radius, float r2, int guides,
                        unsigned char *out, void *stream);
 
+/* ---- a test run's clouds accumulated over a window of frames (cmflow_amd/accumulate.py) -------------------------
+ * cmf_accumulate: for every selected target frame j, the cloud-1 points of the last frames of j's clip brought into j's scan-1
+ * sensor coordinates -- a definition, not an approximation of one.  Frames of a clip [a, b) are consecutive scan pairs: scan 2 of
+ * frame k is scan 1 of frame k+1 (the contract of cmf_pose_chain), and T_k (T (nframes,16) float32, row-major) maps static points
+ * from scan-1 to scan-2 coordinates of frame k.
+ *   frames (nsel) int64 in device memory, ids clamped to [0, nframes-1], the same id may occur twice; NULL: frames 0 .. nsel-1.
+ *   first (nsel) int32: the first frame a of the clip of every selected target, clamped to [0, j].
+ *   off1 / total / tab1 / ld_tab: the split's cloud-1 table (xyz at columns 0..2, label flow 6..8, mask 9; ld_tab >= 10).
+ *   gt == 0: flow (total,3) and mask (total) bytes are the store's, T its trans_pred; a point is MOVING iff its mask byte is 0.
+ *   gt != 0: flow and mask are not read (may be NULL); the flow is tab1's columns 6..8, a point is MOVING iff tab1 column 9 == 0.0f,
+ *            and T is the split's trans.  Every other mask value is static.
+ *   window W, 1 <= W <= CMF_ACCUM_MAX_WINDOW; mode: CMF_ACCUM_KEEP, CMF_ACCUM_PROPAGATE or CMF_ACCUM_DROP.
+ *   cap_off (nsel+1) int32 in device memory, ascending: target s owns output rows cap_off[s] .. cap_off[s+1]-1 (its capacity; the
+ *   host passes the sum of its sources' point counts); cap_total: the rows of the outputs.
+ *   Outputs: xyz (cap_total,3) float32; src (cap_total) int32, the point's row in tab1 / the store; age (cap_total) bytes;
+ *   count (nsel) int32, the rows of the target that hold points.
+ * For target j the ages are g = 0 .. G-1, G = min(W, j - a + 1); the source of age g is frame i = j - g (never across the clip's start).
+ *   Chain, 3x4 float64 from the float32 entries, affine:  M_0 = I,  M_g = M_g-1 . T_j-g:
+ *     c < 3:  M_g[r][c] = (M[r][0] T[0][c] + M[r][1] T[1][c]) + M[r][2] T[2][c]
+ *             M_g[r][3] = ((M[r][0] T[0][3] + M[r][1] T[1][3]) + M[r][2] T[2][3]) + M[r][3]          (M = M_g-1, T = T_j-g)
+ *   M_g takes scan-1 coordinates of frame j-g to scan-1 coordinates of frame j.  No inverse is taken anywhere: a T that is not exactly
+ *   orthonormal is used as it is.
+ *   A point p (float32 xyz) of source i at age g:
+ *     g == 0:                          xyz = p, copied bit for bit
+ *     static, or mode KEEP:            q_r = ((M_g[r][0] px + M_g[r][1] py) + M_g[r][2] pz) + M_g[r][3]
+ *     moving, mode PROPAGATE, g >= 1:  with f its flow, tp_r the same expression with T_i in place of M_g, and N = M_g-1:
+ *                                        d_r = ((double)p_r + (double)f_r) - tp_r
+ *                                        e_r = (N[r][0] d_0 + N[r][1] d_1) + N[r][2] d_2
+ *                                        q_r = q_r + (double)g * e_r
+ *                                      a constant displacement per step in the ego-compensated frame; at g = 1 the flow's endpoint p + f
+ *     moving, mode DROP, g >= 1:       the point is left out
+ *   and xyz_r = (float)q_r.  Every multiplication and addition is rounded on its own (no contraction).
+ *   Row order: oldest age first, the current frame (g = 0) last -- rendered, "the highest index wins" paints the newest scan on top;
+ *   inside an age the source frame's own point order.  tests/accumulate_ref.py restates all of this in numpy, bit for bit.
+ * Guarantees, as cmf_pack_results: every output row inside a target's capacity is written exactly once, by one thread (no atomics):
+ *   the first count[s] rows hold points, the rows behind them xyz 0, src -1, age 255 (only DROP, or a capacity larger than the sources'
+ *   point count, leaves such rows); points that do not fit into the capacity are left out; rows outside every capacity are not touched.
+ *   A source frame whose rows do not lie inside [0, total), and a target whose capacity does not lie inside [0, cap_total), is treated
+ *   as empty: a bad id or offset gives wrong data, never an access outside a buffer.  total, cap_total <= INT_MAX.
+ *   One workgroup per target; the chain is formed once per target by one lane, in order. */
+#define CMF_ACCUM_MAX_WINDOW 64
+#define CMF_ACCUM_KEEP 0
+#define CMF_ACCUM_PROPAGATE 1
+#define CMF_ACCUM_DROP 2
+int cmf_accumulate(int nsel, int nframes, const long long *frames, const int *first, const int *off1, long long total,
+                   const float *tab1, int ld_tab, const float *flow, const unsigned char *mask, const float *T, int window,
+                   int mode, int gt, const int *cap_off, long long cap_total, float *xyz, int *src, unsigned char *age,
+                   int *count, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
