@@ -140,70 +140,50 @@ __global__ __launch_bounds__(64) void eval_finalize_kernel(int b, int n, const d
     }
 }
 
-// Ragged samples: the metrics of every sample on its own -- eval_finalize_kernel's formulae with b = 1, n = cnt[i] -- then their mean
-// over the samples in index order: what main_util.py:176-192 accumulates with the test loader's batch size 1 (main.py:203).
+// The value of metric t for ONE sample from its partial sums s and its point count n: eval_finalize_kernel's formulae with b = 1.
+__device__ __forceinline__ double ev_sample_metric(int t, const double *__restrict__ s, double n)
+{
+    const double mov = s[4] / (s[5] + 1e-6), stat = s[6] / s[7];              // np.mean of an empty selection is NaN
+    const double tp = s[10], tn = s[11], fp = s[12], fn = s[13];
+    switch (t) {
+    case 0: return s[3] / n;
+    case 1: return (mov + stat) / 2.0;
+    case 2: return mov;
+    case 3: return stat;
+    case 4: return s[8] / n;
+    case 5: return s[9] / n;
+    case 6: return s[0] / n;
+    case 7: return s[1] / n;
+    case 8: return s[2] / n;
+    case 9: return (tp + tn) / (((tp + tn) + fp) + fn);
+    case 10: return 0.5 * (tp / (((tp + fp) + fn) + 1e-10) + tn / (((tn + fp) + fn) + 1e-10));
+    case 11: return tp / ((tp + fn) + 1e-10);
+    case 12: return s[14];
+    default: return s[15];
+    }
+}
+
+// Ragged samples: the metrics of every sample on its own, n = cnt[i], then their mean over the samples in index order: what
+// main_util.py:176-192 accumulates with the test loader's batch size 1 (main.py:203).
 __global__ __launch_bounds__(64) void eval_finalize_counted_kernel(int b, int ld, const int *__restrict__ cnt, const double *__restrict__ partial,
                                                                    double *__restrict__ metrics)
 {
     const int t = threadIdx.x;
     if (t >= 14) return;
     double acc = 0.0;
-    for (int i = 0; i < b; ++i) {
-        const double *s = partial + (size_t)i * EV_PART;
-        const double n = (double)max(0, min(cnt[i], ld));
-        const double mov = s[4] / (s[5] + 1e-6), stat = s[6] / s[7];          // np.mean of an empty selection is NaN
-        const double tp = s[10], tn = s[11], fp = s[12], fn = s[13];
-        double v;
-        switch (t) {
-        case 0: v = s[3] / n; break;
-        case 1: v = (mov + stat) / 2.0; break;
-        case 2: v = mov; break;
-        case 3: v = stat; break;
-        case 4: v = s[8] / n; break;
-        case 5: v = s[9] / n; break;
-        case 6: v = s[0] / n; break;
-        case 7: v = s[1] / n; break;
-        case 8: v = s[2] / n; break;
-        case 9: v = (tp + tn) / (((tp + tn) + fp) + fn); break;
-        case 10: v = 0.5 * (tp / (((tp + fp) + fn) + 1e-10) + tn / (((tn + fp) + fn) + 1e-10)); break;
-        case 11: v = tp / ((tp + fn) + 1e-10); break;
-        case 12: v = s[14]; break;
-        default: v = s[15]; break;
-        }
-        acc += v;
-    }
+    for (int i = 0; i < b; ++i)
+        acc += ev_sample_metric(t, partial + (size_t)i * EV_PART, (double)max(0, min(cnt[i], ld)));
     metrics[t] = acc / (double)b;
 }
 
-// Per-frame results (cmf_eval_metrics_frames, cmflow_amd/results.py): eval_finalize_counted_kernel's per-sample value v of metric t,
-// the same expressions in the same order, written to row frames[i] of a (F,14) table instead of being averaged.  One workgroup
-// per sample; frame ids are clamped to [0, F-1].
+// Per-frame results (cmf_eval_metrics_frames, cmflow_amd/results.py): the per-sample value of metric t written to row frames[i] of
+// a (F,14) table instead of being averaged.  One workgroup per sample; frame ids are clamped to [0, F-1].
 __global__ __launch_bounds__(64) void eval_finalize_frames_kernel(int ld, int nframes, const int *__restrict__ cnt, const int *__restrict__ frames,
                                                                   const double *__restrict__ partial, double *__restrict__ table)
 {
     const int i = blockIdx.x, t = threadIdx.x;
     if (t >= 14) return;
-    const double *s = partial + (size_t)i * EV_PART;
-    const double n = (double)max(0, min(cnt[i], ld));
-    const double mov = s[4] / (s[5] + 1e-6), stat = s[6] / s[7];              // np.mean of an empty selection is NaN
-    const double tp = s[10], tn = s[11], fp = s[12], fn = s[13];
-    double v;
-    switch (t) {
-    case 0: v = s[3] / n; break;
-    case 1: v = (mov + stat) / 2.0; break;
-    case 2: v = mov; break;
-    case 3: v = stat; break;
-    case 4: v = s[8] / n; break;
-    case 5: v = s[9] / n; break;
-    case 6: v = s[0] / n; break;
-    case 7: v = s[1] / n; break;
-    case 8: v = s[2] / n; break;
-    case 9: v = (tp + tn) / (((tp + tn) + fp) + fn); break;
-    case 10: v = 0.5 * (tp / (((tp + fp) + fn) + 1e-10) + tn / (((tn + fp) + fn) + 1e-10)); break;
-    case 11: v = tp / ((tp + fn) + 1e-10); break;
-    case 12: v = s[14]; break;
-    default: v = s[15]; break;
-    }
+    const double v = ev_sample_metric(t, partial + (size_t)i * EV_PART, (double)max(0, min(cnt[i], ld)));
     const int f = min(max(frames[i], 0), nframes - 1);
     table[(size_t)f * 14 + t] = v;
 }
@@ -272,53 +252,63 @@ __global__ __launch_bounds__(EV_THREADS) void pseudo_label_kernel(
         }
 }
 
+// cmf_pseudo_labels (cnt == nullptr) and cmf_pseudo_labels_counted
+template <bool COUNTED>
+static int pseudo_labels_launch(int b, int n, const int *cnt, const float *pc1, const float *gt_trans, const float *vel1,
+                                const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
+                                float *dyn_mask, float *mseg_gt, float *residual, void *stream)
+{
+    CMF_CHECK_ARG(b >= 0 && n > 0 && n <= 36000);
+    if (b == 0) return 0;
+    CMF_CHECK_ARG((!COUNTED || cnt) && pc1 && gt_trans && vel1 && interval && fg_mask && flow_label && dyn_mask && mseg_gt);
+    static CmfPerDevice attr_set;                       // the dynamic-LDS limit is per (function, device): one guard per instantiation
+    int attr_dev;
+    if (attr_set.need(attr_dev)) {
+        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel<COUNTED>, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
+        attr_set.done(attr_dev);
+    }
+    hipLaunchKernelGGL(pseudo_label_kernel<COUNTED>, dim3(b), dim3(EV_THREADS), (size_t)n * sizeof(float), (hipStream_t)stream,
+                       n, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, cnt);
+    return cmf_launch_status();
+}
+
 extern "C" int cmf_pseudo_labels(int b, int n, const float *pc1, const float *gt_trans, const float *vel1,
                                  const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
                                  float *dyn_mask, float *mseg_gt, float *residual, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && n > 0 && n <= 36000);
-    if (b == 0) return 0;
-    CMF_CHECK_ARG(pc1 && gt_trans && vel1 && interval && fg_mask && flow_label && dyn_mask && mseg_gt);
-    static CmfPerDevice attr_set;                       // the dynamic-LDS limit is per (function, device)
-    int attr_dev;
-    if (attr_set.need(attr_dev)) {
-        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
-        attr_set.done(attr_dev);
-    }
-    hipLaunchKernelGGL(pseudo_label_kernel<false>, dim3(b), dim3(EV_THREADS), (size_t)n * sizeof(float), (hipStream_t)stream,
-                       n, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, (const int *)nullptr);
-    return cmf_launch_status();
+    return pseudo_labels_launch<false>(b, n, nullptr, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, stream);
 }
 
 extern "C" int cmf_pseudo_labels_counted(int b, int nmax, const int *n1, const float *pc1, const float *gt_trans, const float *vel1,
                                          const float *interval, const float *fg_mask, const float *flow_label, float vr_thres,
                                          float *dyn_mask, float *mseg_gt, float *residual, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && nmax > 0 && nmax <= 36000);
-    if (b == 0) return 0;
-    CMF_CHECK_ARG(n1 && pc1 && gt_trans && vel1 && interval && fg_mask && flow_label && dyn_mask && mseg_gt);
-    static CmfPerDevice attr_set;
-    int attr_dev;
-    if (attr_set.need(attr_dev)) {
-        (void)hipFuncSetAttribute((const void *)pseudo_label_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 36000 * 4);
-        attr_set.done(attr_dev);
-    }
-    hipLaunchKernelGGL(pseudo_label_kernel<true>, dim3(b), dim3(EV_THREADS), (size_t)nmax * sizeof(float), (hipStream_t)stream,
-                       nmax, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, n1);
-    return cmf_launch_status();
+    return pseudo_labels_launch<true>(b, nmax, n1, pc1, gt_trans, vel1, interval, fg_mask, flow_label, vr_thres, dyn_mask, mseg_gt, residual, stream);
+}
+
+// The per-sample sums of the three cmf_eval_metrics* entry points (cnt == nullptr: dense) into workspace; the caller's finalize
+// kernel follows on the same stream.
+template <bool COUNTED>
+static int eval_sample_launch(int b, int n, const int *cnt, const float *pc, const float *pred, const float *labels, const float *mask,
+                              const float *pred_m, const float *gt_trans, const float *pred_trans,
+                              float r_res, float theta_res, float phi_res, const void *out, double *workspace, hipStream_t st)
+{
+    CMF_CHECK_ARG(b > 0 && n > 0 && (!COUNTED || cnt) && out && workspace);
+    // each of the three groups may be left out (NULL): scene flow (pc, pred, labels, mask), segmentation (pred_m,
+    // mask), pose (gt_trans, pred_trans); the metrics of a skipped group are not meaningful
+    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
+    hipLaunchKernelGGL(eval_sample_kernel<COUNTED>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
+                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    return 0;
 }
 
 extern "C" int cmf_eval_metrics(int b, int n, const float *pc, const float *pred, const float *labels, const float *mask,
                                 const float *pred_m, const float *gt_trans, const float *pred_trans,
                                 float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream)
 {
-    CMF_CHECK_ARG(b > 0 && n > 0 && metrics && workspace);
-    // each of the three groups may be left out (NULL): scene flow (pc, pred, labels, mask), segmentation (pred_m,
-    // mask), pose (gt_trans, pred_trans); the metrics of a skipped group are not meaningful
-    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_sample_kernel<false>, dim3(b), dim3(EV_THREADS), 0, st, n, (const int *)nullptr, pc, pred, labels, mask, pred_m, gt_trans,
-                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    if (int err = eval_sample_launch<false>(b, n, nullptr, pc, pred, labels, mask, pred_m, gt_trans, pred_trans, r_res, theta_res, phi_res,
+                                            metrics, workspace, st)) return err;
     hipLaunchKernelGGL(eval_finalize_kernel, dim3(1), dim3(64), 0, st, b, n, workspace, metrics);
     return cmf_launch_status();
 }
@@ -327,11 +317,9 @@ extern "C" int cmf_eval_metrics_counted(int b, int n, const int *cnt, const floa
                                         const float *pred_m, const float *gt_trans, const float *pred_trans,
                                         float r_res, float theta_res, float phi_res, double *metrics, double *workspace, void *stream)
 {
-    CMF_CHECK_ARG(b > 0 && n > 0 && cnt && metrics && workspace);
-    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_sample_kernel<true>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
-                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    if (int err = eval_sample_launch<true>(b, n, cnt, pc, pred, labels, mask, pred_m, gt_trans, pred_trans, r_res, theta_res, phi_res,
+                                           metrics, workspace, st)) return err;
     hipLaunchKernelGGL(eval_finalize_counted_kernel, dim3(1), dim3(64), 0, st, b, n, cnt, workspace, metrics);
     return cmf_launch_status();
 }
@@ -341,11 +329,10 @@ extern "C" int cmf_eval_metrics_frames(int b, int n, const int *cnt, const float
                                        float r_res, float theta_res, float phi_res, int nframes, const int *frames, double *table,
                                        double *workspace, void *stream)
 {
-    CMF_CHECK_ARG(b > 0 && n > 0 && nframes > 0 && cnt && frames && table && workspace);
-    CMF_CHECK_ARG((!pc || (pred && labels && mask)) && (!pred_m || mask) && (!gt_trans || pred_trans));
+    CMF_CHECK_ARG(nframes > 0 && frames);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_sample_kernel<true>, dim3(b), dim3(EV_THREADS), 0, st, n, cnt, pc, pred, labels, mask, pred_m, gt_trans,
-                       pred_trans, (double)r_res, (double)theta_res, (double)phi_res, workspace);
+    if (int err = eval_sample_launch<true>(b, n, cnt, pc, pred, labels, mask, pred_m, gt_trans, pred_trans, r_res, theta_res, phi_res,
+                                           table, workspace, st)) return err;
     hipLaunchKernelGGL(eval_finalize_frames_kernel, dim3(b), dim3(64), 0, st, n, nframes, cnt, frames, workspace, table);
     return cmf_launch_status();
 }

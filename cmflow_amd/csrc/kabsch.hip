@@ -372,26 +372,43 @@ extern "C" int cmf_weighted_kabsch_grad(int b, int n, const float *A, const floa
     return cmf_launch_status();
 }
 
-extern "C" int cmf_ego_refine(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score,
-                              float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask, void *stream)
+// cmf_ego_refine (cnt == nullptr, stat unused) and cmf_ego_refine_counted
+template <bool COUNTED>
+static int ego_refine_launch(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score, const int *cnt,
+                             float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask, float *stat, void *stream)
 {
     CMF_CHECK_ARG(b >= 0 && n > 0);
     if (b == 0) return 0;
-    CMF_CHECK_ARG(pc1 && flow && score && W && Bm && trans && sf && mask);
-    hipLaunchKernelGGL(ego_refine_fwd_kernel<false>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm, trans,
-                       aux, sf, mask, (const int *)nullptr, (float *)nullptr);
+    CMF_CHECK_ARG(pc1 && flow && score && (!COUNTED || cnt) && W && Bm && trans && sf && mask);
+    hipLaunchKernelGGL(ego_refine_fwd_kernel<COUNTED>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm,
+                       trans, aux, sf, mask, cnt, stat);
     return cmf_launch_status();
+}
+
+extern "C" int cmf_ego_refine(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score,
+                              float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask, void *stream)
+{
+    return ego_refine_launch<false>(b, n, eps, thres, pc1, flow, score, nullptr, W, Bm, trans, aux, sf, mask, nullptr, stream);
 }
 
 extern "C" int cmf_ego_refine_counted(int b, int n, float eps, float thres, const float *pc1, const float *flow, const float *score,
                                       const int *cnt, float *W, float *Bm, float *trans, double *aux, float *sf, unsigned char *mask,
                                       float *stat, void *stream)
 {
+    return ego_refine_launch<true>(b, n, eps, thres, pc1, flow, score, cnt, W, Bm, trans, aux, sf, mask, stat, stream);
+}
+
+// cmf_ego_refine_grad (cnt == nullptr) and cmf_ego_refine_grad_counted
+template <bool COUNTED>
+static int ego_refine_grad_launch(int b, int n, float eps, const float *pc1, const float *score, const int *cnt, const float *W,
+                                  const float *Bm, const unsigned char *mask, const double *aux, const float *g_sf, const float *g_trans,
+                                  float *g_flow, float *g_w, float *g_score, void *stream)
+{
     CMF_CHECK_ARG(b >= 0 && n > 0);
     if (b == 0) return 0;
-    CMF_CHECK_ARG(pc1 && flow && score && cnt && W && Bm && trans && sf && mask);
-    hipLaunchKernelGGL(ego_refine_fwd_kernel<true>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, thres, pc1, flow, score, W, Bm, trans,
-                       aux, sf, mask, cnt, stat);
+    CMF_CHECK_ARG(pc1 && score && (!COUNTED || cnt) && W && Bm && mask && aux && g_sf && g_flow && g_w);
+    hipLaunchKernelGGL(ego_refine_bwd_kernel<COUNTED>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux,
+                       g_sf, g_trans, g_flow, g_w, g_score, cnt);
     return cmf_launch_status();
 }
 
@@ -399,24 +416,14 @@ extern "C" int cmf_ego_refine_grad(int b, int n, float eps, const float *pc1, co
                                    const unsigned char *mask, const double *aux, const float *g_sf, const float *g_trans,
                                    float *g_flow, float *g_w, float *g_score, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && n > 0);
-    if (b == 0) return 0;
-    CMF_CHECK_ARG(pc1 && score && W && Bm && mask && aux && g_sf && g_flow && g_w);
-    hipLaunchKernelGGL(ego_refine_bwd_kernel<false>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux, g_sf,
-                       g_trans, g_flow, g_w, g_score, (const int *)nullptr);
-    return cmf_launch_status();
+    return ego_refine_grad_launch<false>(b, n, eps, pc1, score, nullptr, W, Bm, mask, aux, g_sf, g_trans, g_flow, g_w, g_score, stream);
 }
 
 extern "C" int cmf_ego_refine_grad_counted(int b, int n, float eps, const float *pc1, const float *score, const int *cnt, const float *W,
                                            const float *Bm, const unsigned char *mask, const double *aux, const float *g_sf,
                                            const float *g_trans, float *g_flow, float *g_w, float *g_score, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && n > 0);
-    if (b == 0) return 0;
-    CMF_CHECK_ARG(pc1 && score && cnt && W && Bm && mask && aux && g_sf && g_flow && g_w);
-    hipLaunchKernelGGL(ego_refine_bwd_kernel<true>, dim3(b), dim3(CMF_WAVE), 0, (hipStream_t)stream, n, eps, pc1, score, W, Bm, mask, aux, g_sf,
-                       g_trans, g_flow, g_w, g_score, cnt);
-    return cmf_launch_status();
+    return ego_refine_grad_launch<true>(b, n, eps, pc1, score, cnt, W, Bm, mask, aux, g_sf, g_trans, g_flow, g_w, g_score, stream);
 }
 
 // test-only stream delay (cmflow_hip.h): one wave polling the constant-frequency clock

@@ -505,63 +505,34 @@ struct BqMultiArgs {
     int *idx[2][4];
 };
 
-template <int NCH>
-__global__ __launch_bounds__(BQB_WAVES *CMF_WAVE) void ball_query_multi_ballot_kernel(const BqMultiArgs a)
-{
-    extern __shared__ int bqb_lds[];                          // [BQB_WAVES][G * sum(nsample)]
-    const int bs = blockIdx.y, cl = blockIdx.z, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pt0 = (blockIdx.x * BQB_WAVES + w) * a.G;
-    if (pt0 >= a.m) return;                                   // wave-uniform; no workgroup barrier anywhere
-    BqbCloud<NCH> cloud;
-    bqb_load_cloud<NCH>(a.xyz[cl] + (size_t)bs * a.n * 3, a.n, lane, cloud);
-    int *lst = bqb_lds + w * a.G * a.lst_off[a.nq];
-    const int gv = min(a.G, a.m - pt0);
-    unsigned empty[4] = {0u, 0u, 0u, 0u};
-    for (int g = 0; g < gv; ++g) {
-        const float *cc = a.new_xyz[cl] + ((size_t)bs * a.m + pt0 + g) * 3;
-        const float cx = cc[0], cy = cc[1], cz = cc[2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < a.nq && bqb_centre<NCH>(cloud, cx, cy, cz, a.r2[q], a.ns[q], lane, lst + a.G * a.lst_off[q] + g * a.ns[q]) == 0) empty[q] |= 1u << g;
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q >= a.nq) break;
-        const int ns = a.ns[q];
-        int *out = a.idx[cl][q] + ((size_t)bs * a.m + pt0) * ns;
-        const int *src = lst + a.G * a.lst_off[q];
-        for (int e = lane; e < gv * ns; e += CMF_WAVE) {
-            if (!((empty[q] >> (e / ns)) & 1u)) out[e] = src[e];
-            else if (a.zero_empty) out[e] = 0;
-        }
-    }
-}
-
-// The same launch over RAGGED samples (the reference's test protocol, main.py:203 + dataset/vod.py:92-111: whole frames of their own
-// sizes): sample bs of cloud cl holds n_src[cl][bs] <= n points and n_ctr[cl][bs] <= m centres, the rest of its rows is padding.
-// Candidates are the sample's own points only -- the slots behind them are loaded as +inf like the slots behind n in the dense
-// form, so every list of a valid centre is what cmf_ball_query returns on the truncated sample, bit for bit -- and the rows of
-// padded centres (and of empty balls) are written as zeros.  The counts are read from a wave-uniform address (one sample per
-// workgroup row): the number of live centres is a scalar, no lane diverges on it.  The chunk count NCH follows the padded
-// size like the dense launch's; chunks behind a short sample hold +inf only and cost four compares each.
+// COUNTED, the same launch over RAGGED samples (the reference's test protocol, main.py:203 + dataset/vod.py:92-111: whole frames of
+// their own sizes): sample bs of cloud cl holds n_src[cl][bs] <= n points and n_ctr[cl][bs] <= m centres, the rest of its rows is
+// padding.  Candidates are the sample's own points only -- the slots behind them are loaded as +inf like the slots behind n in the
+// dense form, so every list of a valid centre is what cmf_ball_query returns on the truncated sample, bit for bit -- and the rows of
+// padded centres (and of empty balls) are written as zeros; a wave without a live centre does not load the cloud.  The counts are
+// read from a wave-uniform address (one sample per workgroup row): the number of live centres is a scalar, no lane diverges on it.
+// The chunk count NCH follows the padded size like the dense launch's; chunks behind a short sample hold +inf only and cost four
+// compares each.  Dense: cn is not read, every centre of the wave is live and empty balls follow zero_empty.
 struct BqCounts { const int *n_ctr[2], *n_src[2]; };
 
-template <int NCH>
-__global__ __launch_bounds__(BQB_WAVES *CMF_WAVE) void ball_query_multi_counted_kernel(const BqMultiArgs a, const BqCounts cn)
+template <int NCH, bool COUNTED>
+__global__ __launch_bounds__(BQB_WAVES *CMF_WAVE) void ball_query_multi_ballot_kernel(const BqMultiArgs a, const BqCounts cn)
 {
     extern __shared__ int bqb_lds[];                          // [BQB_WAVES][G * sum(nsample)]
     const int bs = blockIdx.y, cl = blockIdx.z, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int pt0 = (blockIdx.x * BQB_WAVES + w) * a.G;
     if (pt0 >= a.m) return;                                   // wave-uniform; no workgroup barrier anywhere
-    const int nsrc = max(0, min(cn.n_src[cl][bs], a.n)), nctr = max(0, min(cn.n_ctr[cl][bs], a.m));
+    // (where the cloud is loaded and declared live decides the register allocation: each form loads it where its own kernel did)
+    BqbCloud<NCH> cloud;
+    int nsrc = 0, nctr = 0;
+    if (COUNTED) { nsrc = max(0, min(cn.n_src[cl][bs], a.n)); nctr = max(0, min(cn.n_ctr[cl][bs], a.m)); }
+    else bqb_load_cloud<NCH>(a.xyz[cl] + (size_t)bs * a.n * 3, a.n, lane, cloud);
     int *lst = bqb_lds + w * a.G * a.lst_off[a.nq];
     const int gv = min(a.G, a.m - pt0);
-    const int gl = max(0, min(gv, nctr - pt0));               // centres of this wave that are points of the sample
+    const int gl = COUNTED ? max(0, min(gv, nctr - pt0)) : gv;    // centres of this wave that are points of the sample
     unsigned empty[4] = {0u, 0u, 0u, 0u};
-    if (gl > 0) {
-        BqbCloud<NCH> cloud;
-        bqb_load_cloud<NCH>(a.xyz[cl] + (size_t)bs * a.n * 3, nsrc, lane, cloud);
+    if (!COUNTED || gl > 0) {
+        if (COUNTED) bqb_load_cloud<NCH>(a.xyz[cl] + (size_t)bs * a.n * 3, nsrc, lane, cloud);
         for (int g = 0; g < gl; ++g) {
             const float *cc = a.new_xyz[cl] + ((size_t)bs * a.m + pt0 + g) * 3;
             const float cx = cc[0], cy = cc[1], cz = cc[2];
@@ -580,7 +551,9 @@ __global__ __launch_bounds__(BQB_WAVES *CMF_WAVE) void ball_query_multi_counted_
         const int *src = lst + a.G * a.lst_off[q];
         for (int e = lane; e < gv * ns; e += CMF_WAVE) {
             const int g = e / ns;
-            out[e] = (g < gl && !((empty[q] >> g) & 1u)) ? src[e] : 0;
+            if (COUNTED) out[e] = (g < gl && !((empty[q] >> g) & 1u)) ? src[e] : 0;
+            else if (!((empty[q] >> g) & 1u)) out[e] = src[e];
+            else if (a.zero_empty) out[e] = 0;
         }
     }
 }
@@ -752,6 +725,15 @@ bool cmf_ball_query_multi_takes(int n, int nq, const int *nsamples)
     return (size_t)BQB_WAVES * tot * sizeof(int) <= BQB_LDS_LIMIT;
 }
 
+// the chunk count follows the (padded) cloud size
+template <bool COUNTED>
+static void bq_multi_ladder(int n, dim3 grid, dim3 block, size_t lds, hipStream_t st, const BqMultiArgs &a, const BqCounts &cn)
+{
+    if (n <= 256) hipLaunchKernelGGL((ball_query_multi_ballot_kernel<1, COUNTED>), grid, block, lds, st, a, cn);
+    else if (n <= 512) hipLaunchKernelGGL((ball_query_multi_ballot_kernel<2, COUNTED>), grid, block, lds, st, a, cn);
+    else hipLaunchKernelGGL((ball_query_multi_ballot_kernel<4, COUNTED>), grid, block, lds, st, a, cn);
+}
+
 // nq <= 4 ball queries (radii[q], nsamples[q]) -> idx[c][q] (B, M, nsamples[q]) over the same centres and cloud, for nclouds <= 2
 // (centres, cloud) pairs of equal geometry, in ONE launch; every list equals cmf_ball_query's for that scale.  zero_empty != 0: the
 // rows of empty balls are written as zeros (a caller that does not pre-zero idx).  Clouds of up to 1024 points (the ballot kernel).
@@ -784,17 +766,11 @@ static int ball_query_multi_launch(int b, int n, int m, int nq, const float *rad
     const dim3 grid(cmf_divup(m, a.G * BQB_WAVES), b, nclouds), block(BQB_WAVES * CMF_WAVE);
     const size_t lds = (size_t)BQB_WAVES * a.G * tot * sizeof(int);
     hipStream_t st = (hipStream_t)stream;
-    if (n_ctr) {                                              // ragged samples: per-sample counts in device memory
-        BqCounts cn{};
+    BqCounts cn{};
+    if (n_ctr)                                                // ragged samples: per-sample counts in device memory
         for (int c = 0; c < nclouds; ++c) { CMF_CHECK_ARG(n_ctr[c] && n_src && n_src[c]); cn.n_ctr[c] = n_ctr[c]; cn.n_src[c] = n_src[c]; }
-        if (n <= 256) hipLaunchKernelGGL(ball_query_multi_counted_kernel<1>, grid, block, lds, st, a, cn);
-        else if (n <= 512) hipLaunchKernelGGL(ball_query_multi_counted_kernel<2>, grid, block, lds, st, a, cn);
-        else hipLaunchKernelGGL(ball_query_multi_counted_kernel<4>, grid, block, lds, st, a, cn);
-        return cmf_launch_status();
-    }
-    if (n <= 256) hipLaunchKernelGGL(ball_query_multi_ballot_kernel<1>, grid, block, lds, st, a);
-    else if (n <= 512) hipLaunchKernelGGL(ball_query_multi_ballot_kernel<2>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(ball_query_multi_ballot_kernel<4>, grid, block, lds, st, a);
+    if (n_ctr) bq_multi_ladder<true>(n, grid, block, lds, st, a, cn);
+    else bq_multi_ladder<false>(n, grid, block, lds, st, a, cn);
     return cmf_launch_status();
 }
 
@@ -881,16 +857,21 @@ __device__ __forceinline__ float sqnorm3(float x, float y, float z)
 // PLAIN = true : the extension's knn / three_nn kernels (lib/src/interpolate_gpu.cu:9-57,81-124), which use the
 //                direct form d = (ux-x)^2 + (uy-y)^2 + (uz-z)^2 (non-contracted here) and keep the first-seen
 //                point on ties -- identical bookkeeping, only the distance differs.
-template <int K, bool PLAIN>
+// COUNTED (cmf_knn_counted, ragged samples): the sample's rows are ld apart in memory and the scan runs over its first n_src[bs]
+// rows (one sample per workgroup row: a scalar) -- the same statements in the same order, so the lists equal cmf_knn's on the
+// truncated sample bit for bit.  Padded QUERY rows get lists too (valid rows of their own sample); nothing reads them.
+// Dense: n == ld and n_src is not read; it is the LAST argument, so the dense form's arguments sit where a kernel without it has them.
+template <int K, bool PLAIN, bool COUNTED>
 __global__ __launch_bounds__(CMF_WAVE) void knn_kernel(
-    int n, int s, int nsample, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
-    int *__restrict__ idx, float *__restrict__ dist)
+    int ld, int s, int nsample, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+    int *__restrict__ idx, float *__restrict__ dist, const int *__restrict__ n_src)
 {
+    const int n = COUNTED ? max(0, min(n_src[blockIdx.y], ld)) : ld;    // wave-uniform: the scan's trip count
     __shared__ float4 tile[KNN_TILE];
     const int bs = blockIdx.y;
     const int q = blockIdx.x * CMF_WAVE + threadIdx.x;
     const bool live = q < s;
-    const float *pts = xyz + (size_t)bs * n * 3;
+    const float *pts = xyz + (size_t)bs * ld * 3;
     float qx = 0.f, qy = 0.f, qz = 0.f;
     if (live) {
         const float *c = new_xyz + ((size_t)bs * s + q) * 3;
@@ -960,111 +941,36 @@ __global__ __launch_bounds__(CMF_WAVE) void knn_kernel(
     }
 }
 
-extern "C" int cmf_knn(int b, int n, int s, int nsample, const float *xyz, const float *new_xyz,
-                       int *idx, float *dist, void *stream)
+// cmf_knn (n_src == nullptr) and cmf_knn_counted: the checks and the list-length ladder
+template <bool COUNTED>
+static int knn_launch(int b, int n, int s, int nsample, const float *xyz, const float *new_xyz, const int *n_src,
+                      int *idx, float *dist, void *stream)
 {
     CMF_CHECK_ARG(b >= 0 && n >= 0 && s >= 0 && nsample > 0 && nsample <= 32);
     if (b == 0 || s == 0) return 0;
-    CMF_CHECK_ARG(xyz && new_xyz && idx);
+    CMF_CHECK_ARG(xyz && new_xyz && idx && (!COUNTED || n_src));
     dim3 grid(cmf_divup(s, CMF_WAVE), b), block(CMF_WAVE);
     hipStream_t st = (hipStream_t)stream;
     // the list length is a compile-time constant so it stays in registers; the list is sorted,
     // so running a longer list and emitting its first nsample entries is exact.
-    if (nsample <= 1)       hipLaunchKernelGGL((knn_kernel<1, false>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist);
-    else if (nsample <= 4)  hipLaunchKernelGGL((knn_kernel<4, false>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist);
-    else if (nsample <= 8)  hipLaunchKernelGGL((knn_kernel<8, false>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist);
-    else if (nsample <= 16) hipLaunchKernelGGL((knn_kernel<16, false>), grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist);
-    else                    hipLaunchKernelGGL((knn_kernel<32, false>), grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist);
+    if (nsample <= 1)       hipLaunchKernelGGL((knn_kernel<1, false, COUNTED>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist, n_src);
+    else if (nsample <= 4)  hipLaunchKernelGGL((knn_kernel<4, false, COUNTED>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist, n_src);
+    else if (nsample <= 8)  hipLaunchKernelGGL((knn_kernel<8, false, COUNTED>),  grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist, n_src);
+    else if (nsample <= 16) hipLaunchKernelGGL((knn_kernel<16, false, COUNTED>), grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist, n_src);
+    else                    hipLaunchKernelGGL((knn_kernel<32, false, COUNTED>), grid, block, 0, st, n, s, nsample, xyz, new_xyz, idx, dist, n_src);
     return cmf_launch_status();
 }
 
-// kNN over RAGGED samples (cmf_knn_counted): knn_kernel<K, false> with the sample's rows ld apart in memory and its own count as the
-// scan's length -- the same statements in the same order, so the lists equal cmf_knn's on the truncated sample bit for bit.  Its own
-// kernel rather than a parameter of knn_kernel: the dense kernel keeps its code and its name (tests/test_build.py looks the symbol up).  Padded QUERY rows get lists too (valid
-// rows of their own sample); nothing reads them.
-template <int K>
-__global__ __launch_bounds__(CMF_WAVE) void knn_counted_kernel(
-    int ld, int s, int nsample, const float *__restrict__ xyz, const float *__restrict__ new_xyz, const int *__restrict__ n_src,
-    int *__restrict__ idx, float *__restrict__ dist)
+extern "C" int cmf_knn(int b, int n, int s, int nsample, const float *xyz, const float *new_xyz,
+                       int *idx, float *dist, void *stream)
 {
-    const int n = max(0, min(n_src[blockIdx.y], ld));           // wave-uniform (one sample per workgroup row): the scan's trip count
-    __shared__ float4 tile[KNN_TILE];
-    const int bs = blockIdx.y;
-    const int q = blockIdx.x * CMF_WAVE + threadIdx.x;
-    const bool live = q < s;
-    const float *pts = xyz + (size_t)bs * ld * 3;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (live) {
-        const float *c = new_xyz + ((size_t)bs * s + q) * 3;
-        qx = c[0]; qy = c[1]; qz = c[2];
-    }
-    const float ss = sqnorm3(qx, qy, qz);
-    float bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inff(); bi[t] = 0; }
-
-    for (int base = 0; base < n; base += KNN_TILE) {
-        const int len = min(KNN_TILE, n - base);
-        __syncthreads();
-        for (int i = threadIdx.x; i < len; i += CMF_WAVE) {
-            const float x = pts[(size_t)(base + i) * 3 + 0];
-            const float y = pts[(size_t)(base + i) * 3 + 1];
-            const float z = pts[(size_t)(base + i) * 3 + 2];
-            tile[i] = make_float4(x, y, z, sqnorm3(x, y, z));
-        }
-        __syncthreads();
-        for (int k = 0; k < len; ++k) {
-            const float4 p = tile[k];
-            float v;
-            const float p0 = qx * p.x;
-            const float p01 = __builtin_fmaf(qy, p.y, p0);
-            const float dot = __builtin_fmaf(qz, p.z, p01);
-            const float t = -2.0f * dot;
-            const float u = t + ss;
-            v = u + p.w;
-            v = (v > 0.0f) ? v : 0.0f;
-            if (v < bd[K - 1]) {
-                bd[K - 1] = v;
-                bi[K - 1] = base + k;
-#pragma unroll
-                for (int j = K - 1; j > 0; --j) {
-                    if (bd[j] < bd[j - 1]) {
-                        const float td = bd[j]; bd[j] = bd[j - 1]; bd[j - 1] = td;
-                        const int ti = bi[j]; bi[j] = bi[j - 1]; bi[j - 1] = ti;
-                    }
-                }
-            }
-        }
-    }
-    if (live) {
-        int *o = idx + ((size_t)bs * s + q) * nsample;
-#pragma unroll
-        for (int t = 0; t < K; ++t)
-            if (t < nsample) o[t] = (bd[t] == __builtin_inff()) ? 0 : bi[t];
-        if (dist) {
-            float *d = dist + ((size_t)bs * s + q) * nsample;
-#pragma unroll
-            for (int t = 0; t < K; ++t)
-                if (t < nsample) d[t] = (bd[t] == __builtin_inff()) ? 0.0f : bd[t];
-        }
-    }
+    return knn_launch<false>(b, n, s, nsample, xyz, new_xyz, nullptr, idx, dist, stream);
 }
 
 extern "C" int cmf_knn_counted(int b, int n, int s, int nsample, const float *xyz, const float *new_xyz, const int *n_src,
                                int *idx, float *dist, void *stream)
 {
-    CMF_CHECK_ARG(b >= 0 && n >= 0 && s >= 0 && nsample > 0 && nsample <= 32);
-    if (b == 0 || s == 0) return 0;
-    CMF_CHECK_ARG(xyz && new_xyz && idx && n_src);
-    dim3 grid(cmf_divup(s, CMF_WAVE), b), block(CMF_WAVE);
-    hipStream_t st = (hipStream_t)stream;
-    if (nsample <= 1)       hipLaunchKernelGGL(knn_counted_kernel<1>,  grid, block, 0, st, n, s, nsample, xyz, new_xyz, n_src, idx, dist);
-    else if (nsample <= 4)  hipLaunchKernelGGL(knn_counted_kernel<4>,  grid, block, 0, st, n, s, nsample, xyz, new_xyz, n_src, idx, dist);
-    else if (nsample <= 8)  hipLaunchKernelGGL(knn_counted_kernel<8>,  grid, block, 0, st, n, s, nsample, xyz, new_xyz, n_src, idx, dist);
-    else if (nsample <= 16) hipLaunchKernelGGL(knn_counted_kernel<16>, grid, block, 0, st, n, s, nsample, xyz, new_xyz, n_src, idx, dist);
-    else                    hipLaunchKernelGGL(knn_counted_kernel<32>, grid, block, 0, st, n, s, nsample, xyz, new_xyz, n_src, idx, dist);
-    return cmf_launch_status();
+    return knn_launch<true>(b, n, s, nsample, xyz, new_xyz, n_src, idx, dist, stream);
 }
 
 // ---- rest of the pointnet2_cuda neighbour surface (not called by CMFlow) -------------------
@@ -1187,11 +1093,11 @@ extern "C" int cmf_knn_points(int b, int n, int m, int k, const float *unknown, 
         return cmf_launch_status();
     }
     dim3 grid(cmf_divup(n, CMF_WAVE), b), block(CMF_WAVE);
-    if (k <= 4)       hipLaunchKernelGGL((knn_kernel<4, true>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
-    else if (k <= 8)  hipLaunchKernelGGL((knn_kernel<8, true>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
-    else if (k <= 16) hipLaunchKernelGGL((knn_kernel<16, true>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
-    else if (k <= 32) hipLaunchKernelGGL((knn_kernel<32, true>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
-    else              hipLaunchKernelGGL((knn_kernel<64, true>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2);
+    if (k <= 4)       hipLaunchKernelGGL((knn_kernel<4, true, false>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2, (const int *)nullptr);
+    else if (k <= 8)  hipLaunchKernelGGL((knn_kernel<8, true, false>),  grid, block, 0, st, m, n, k, known, unknown, idx, dist2, (const int *)nullptr);
+    else if (k <= 16) hipLaunchKernelGGL((knn_kernel<16, true, false>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2, (const int *)nullptr);
+    else if (k <= 32) hipLaunchKernelGGL((knn_kernel<32, true, false>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2, (const int *)nullptr);
+    else              hipLaunchKernelGGL((knn_kernel<64, true, false>), grid, block, 0, st, m, n, k, known, unknown, idx, dist2, (const int *)nullptr);
     return cmf_launch_status();
 }
 

@@ -1379,47 +1379,53 @@ __global__ __launch_bounds__(GM_THREADS) void global_max_cat_grad_kernel(
     }
 }
 
-extern "C" int cmf_global_max_cat(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg, void *stream)
+// cmf_global_max_cat (cnt == nullptr) and cmf_global_max_cat_counted
+template <bool COUNTED>
+static int global_max_cat_launch(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg, const int *cnt,
+                                 void *stream)
 {
     CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldo >= 2 * C && ldf % 4 == 0 && ldo % 4 == 0 && B < 65536);
     if (B == 0) return 0;
-    CMF_CHECK_ARG(f && out && arg && (((uintptr_t)f | (uintptr_t)out | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_kernel<false>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out, ldo, arg,
-                       (const int *)nullptr);
+    CMF_CHECK_ARG(f && out && arg && (!COUNTED || cnt) && (((uintptr_t)f | (uintptr_t)out | (uintptr_t)arg) & 15) == 0);
+    hipLaunchKernelGGL(global_max_cat_kernel<COUNTED>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out,
+                       ldo, arg, cnt);
     return cmf_launch_status();
+}
+
+extern "C" int cmf_global_max_cat(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg, void *stream)
+{
+    return global_max_cat_launch<false>(B, N, C, f, ldf, out, ldo, arg, nullptr, stream);
 }
 
 extern "C" int cmf_global_max_cat_counted(int B, int N, int C, const float *f, long long ldf, float *out, long long ldo, int *arg,
                                           const int *cnt, void *stream)
 {
-    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldo >= 2 * C && ldf % 4 == 0 && ldo % 4 == 0 && B < 65536);
+    return global_max_cat_launch<true>(B, N, C, f, ldf, out, ldo, arg, cnt, stream);
+}
+
+// cmf_global_max_cat_grad (cnt == nullptr) and cmf_global_max_cat_grad_counted
+template <bool COUNTED>
+static int global_max_cat_grad_launch(int B, int N, int C, const float *dout, long long ldd, const int *arg, float *df, long long ldf,
+                                      const int *cnt, void *stream)
+{
+    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldd >= 2 * C && ldf % 4 == 0 && ldd % 4 == 0 && B < 65536);
     if (B == 0) return 0;
-    CMF_CHECK_ARG(f && out && arg && cnt && (((uintptr_t)f | (uintptr_t)out | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_kernel<true>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, f, ldf, out,
-                       ldo, arg, cnt);
+    CMF_CHECK_ARG(dout && df && arg && (!COUNTED || cnt) && (((uintptr_t)dout | (uintptr_t)df | (uintptr_t)arg) & 15) == 0);
+    hipLaunchKernelGGL(global_max_cat_grad_kernel<COUNTED>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout,
+                       ldd, arg, df, ldf, cnt);
     return cmf_launch_status();
 }
 
 extern "C" int cmf_global_max_cat_grad(int B, int N, int C, const float *dout, long long ldd, const int *arg, float *df, long long ldf,
                                        void *stream)
 {
-    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldd >= 2 * C && ldf % 4 == 0 && ldd % 4 == 0 && B < 65536);
-    if (B == 0) return 0;
-    CMF_CHECK_ARG(dout && df && arg && (((uintptr_t)dout | (uintptr_t)df | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_grad_kernel<false>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout, ldd, arg,
-                       df, ldf, (const int *)nullptr);
-    return cmf_launch_status();
+    return global_max_cat_grad_launch<false>(B, N, C, dout, ldd, arg, df, ldf, nullptr, stream);
 }
 
 extern "C" int cmf_global_max_cat_grad_counted(int B, int N, int C, const float *dout, long long ldd, const int *arg, float *df, long long ldf,
                                                const int *cnt, void *stream)
 {
-    CMF_CHECK_ARG(B >= 0 && N > 0 && C > 0 && C % 4 == 0 && ldf >= C && ldd >= 2 * C && ldf % 4 == 0 && ldd % 4 == 0 && B < 65536);
-    if (B == 0) return 0;
-    CMF_CHECK_ARG(dout && df && arg && cnt && (((uintptr_t)dout | (uintptr_t)df | (uintptr_t)arg) & 15) == 0);
-    hipLaunchKernelGGL(global_max_cat_grad_kernel<true>, dim3(cmf_divup(C, GM_CH), B), dim3(GM_THREADS), 0, (hipStream_t)stream, N, C, dout, ldd,
-                       arg, df, ldf, cnt);
-    return cmf_launch_status();
+    return global_max_cat_grad_launch<true>(B, N, C, dout, ldd, arg, df, ldf, cnt, stream);
 }
 
 // ---- stacked first-conv weights -----------------------------------------------------------------------------

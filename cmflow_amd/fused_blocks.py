@@ -1472,51 +1472,32 @@ class WeightNetKSumFn(Function):
         return dh, dwl, dbl, dx, None, None, dxb, dhb
 
 
+def _global_max_cat_forward(f, counts):
+    """cmf_global_max_cat (counts None) / cmf_global_max_cat_counted -> out (B,N,2C), arg (B,C) int32: the first row attaining the maximum"""
+    B, N, C = f.shape
+    f = f.contiguous()
+    out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
+    arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
+    if counts is None:
+        _lib.check(L().cmf_global_max_cat(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.stream_ptr()), "cmf_global_max_cat")
+    else:
+        _lib.check(L().cmf_global_max_cat_counted(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.dev_ptr(counts, torch.int32),
+                                                  _lib.stream_ptr()), "cmf_global_max_cat_counted")
+    return out, arg
+
+
 class GlobalMaxCatFn(Function):
     """(B,N,C) -> (B,N,2C) = cat(f, max over the points broadcast to every point): Backbone's global feature
     (cmflow.py:76-81,89-91) in one kernel per direction -- cmf_global_max_cat(_grad), csrc/pointwise.hip.  The incoming
-    gradient may be a column block of a wider tensor (row-strided view); it is read in place."""
-
-    @staticmethod
-    def forward(ctx, f):
-        B, N, C = f.shape
-        f = f.contiguous()
-        out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
-        arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
-        _lib.check(L().cmf_global_max_cat(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.stream_ptr()), "cmf_global_max_cat")
-        ctx.arg = arg
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        B, C = ctx.arg.shape
-        N = dout.shape[1]
-        if not (dout.stride(2) == 1 and dout.stride(0) == N * dout.stride(1) and dout.stride(1) % 4 == 0 and dout.data_ptr() % 16 == 0):
-            dout = dout.contiguous()
-        df = torch.empty(B, N, C, dtype=_f32, device=dout.device)
-        _lib.check(L().cmf_global_max_cat_grad(B, N, C, dout.data_ptr(), dout.stride(1), _p(ctx.arg), _p(df), C, _lib.stream_ptr()),
-                   "cmf_global_max_cat_grad")
-        return df
-
-
-def global_max_cat(f):
-    return GlobalMaxCatFn.apply(f)
-
-
-class GlobalMaxCatCountedFn(Function):
-    """GlobalMaxCatFn over RAGGED samples: f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows below each
-    sample's count; backward is cmf_global_max_cat_grad_counted (the broadcast half summed over the valid rows only, padded rows of
-    the gradient zero), reading a row-strided incoming gradient in place like the dense node."""
+    gradient may be a column block of a wider tensor (row-strided view); it is read in place.
+    counts (B,) int32 instead of None: RAGGED samples of Nmax = N padded rows -- the maximum over the rows below each sample's count;
+    backward is cmf_global_max_cat_grad_counted (the broadcast half summed over the valid rows only, padded rows of the gradient
+    zero)."""
 
     @staticmethod
     def forward(ctx, f, counts):
-        B, N, C = f.shape
-        f = f.contiguous()
-        out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
-        arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
-        _lib.check(L().cmf_global_max_cat_counted(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.dev_ptr(counts, torch.int32),
-                                                  _lib.stream_ptr()), "cmf_global_max_cat_counted")
-        ctx.arg, ctx.counts = arg, counts
+        out, ctx.arg = _global_max_cat_forward(f, counts)
+        ctx.counts = counts
         return out
 
     @staticmethod
@@ -1526,22 +1507,27 @@ class GlobalMaxCatCountedFn(Function):
         if not (dout.stride(2) == 1 and dout.stride(0) == N * dout.stride(1) and dout.stride(1) % 4 == 0 and dout.data_ptr() % 16 == 0):
             dout = dout.contiguous()
         df = torch.empty(B, N, C, dtype=_f32, device=dout.device)
-        _lib.check(L().cmf_global_max_cat_grad_counted(B, N, C, dout.data_ptr(), dout.stride(1), _p(ctx.arg), _p(df), C,
-                                                       _lib.dev_ptr(ctx.counts, torch.int32), _lib.stream_ptr()),
-                   "cmf_global_max_cat_grad_counted")
+        if ctx.counts is None:
+            _lib.check(L().cmf_global_max_cat_grad(B, N, C, dout.data_ptr(), dout.stride(1), _p(ctx.arg), _p(df), C, _lib.stream_ptr()),
+                       "cmf_global_max_cat_grad")
+        else:
+            _lib.check(L().cmf_global_max_cat_grad_counted(B, N, C, dout.data_ptr(), dout.stride(1), _p(ctx.arg), _p(df), C,
+                                                           _lib.dev_ptr(ctx.counts, torch.int32), _lib.stream_ptr()),
+                       "cmf_global_max_cat_grad_counted")
         return df, None
+
+
+def global_max_cat(f):
+    return GlobalMaxCatFn.apply(f, None)
 
 
 def global_max_cat_counted(f, counts, want_arg=False):
     """global_max_cat over RAGGED samples: f (B,Nmax,C), counts (B,) int32 -> (B,Nmax,2C) with the maximum over the rows
     below each sample's count (cmf_global_max_cat_counted); want_arg: also the (B,C) int32 first row attaining it.  With autograd
-    recording and f needing a gradient: the GlobalMaxCatCountedFn node."""
+    recording and f needing a gradient: the GlobalMaxCatFn node."""
+    if counts is None:
+        raise RuntimeError("cmf_global_max_cat_counted failed: no per-sample counts")
     if torch.is_grad_enabled() and f.requires_grad and not want_arg:
-        return GlobalMaxCatCountedFn.apply(f, counts)
-    B, N, C = f.shape
-    f = f.contiguous()
-    out = torch.empty(B, N, 2 * C, dtype=_f32, device=f.device)
-    arg = torch.empty(B, C, dtype=torch.int32, device=f.device)
-    _lib.check(L().cmf_global_max_cat_counted(B, N, C, _p(f), C, _p(out), 2 * C, _p(arg), _lib.dev_ptr(counts, torch.int32),
-                                              _lib.stream_ptr()), "cmf_global_max_cat_counted")
+        return GlobalMaxCatFn.apply(f, counts)
+    out, arg = _global_max_cat_forward(f, counts)
     return (out, arg) if want_arg else out

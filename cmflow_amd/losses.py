@@ -21,12 +21,11 @@ from torch.nn import Module
 from . import _lib
 
 
-def make_labels(batch, vr_thres):
-    """main_util.py:63-67: dyn_mask and the merged pseudo motion-segmentation label -- one launch of
-    cmf_pseudo_labels (csrc/eval.hip) on device tensors."""
+def _make_labels(batch, vr_thres, n1, who):
+    """cmf_pseudo_labels (n1 None) / cmf_pseudo_labels_counted (csrc/eval.hip) on device tensors -> dyn_mask, mseg_gt"""
     pc1 = batch["pc1"]
     if not pc1.is_cuda:
-        raise RuntimeError("cmflow_amd.losses.make_labels runs on the GPU only (got %s tensors)" % pc1.device)
+        raise RuntimeError("cmflow_amd.losses.%s runs on the GPU only (got %s tensors)" % (who, pc1.device))
     B, _, N = pc1.shape
     f32 = torch.float32
     c = lambda t: t.to(f32).contiguous()
@@ -34,9 +33,18 @@ def make_labels(batch, vr_thres):
     fg, fl = c(batch["fg_mask"]), c(batch["flow_label"])
     dyn_mask, mseg_gt = torch.empty(B, N, dtype=f32, device=pc1.device), torch.empty(B, N, dtype=f32, device=pc1.device)
     p = lambda t: _lib.dev_ptr(t, f32)
-    _lib.check(_lib.lib().cmf_pseudo_labels(B, N, p(pc), p(T), p(vel), p(dt), p(fg), p(fl), vr_thres, p(dyn_mask),
-                                            p(mseg_gt), None, _lib.stream_ptr()), "cmf_pseudo_labels")
+    rest = (p(pc), p(T), p(vel), p(dt), p(fg), p(fl), vr_thres, p(dyn_mask), p(mseg_gt), None, _lib.stream_ptr())
+    if n1 is None:
+        _lib.check(_lib.lib().cmf_pseudo_labels(B, N, *rest), "cmf_pseudo_labels")
+    else:
+        _lib.check(_lib.lib().cmf_pseudo_labels_counted(B, N, _lib.dev_ptr(n1.contiguous(), torch.int32), *rest), "cmf_pseudo_labels_counted")
     return dyn_mask.to(batch["fg_mask"].dtype), mseg_gt
+
+
+def make_labels(batch, vr_thres):
+    """main_util.py:63-67: dyn_mask and the merged pseudo motion-segmentation label -- one launch of
+    cmf_pseudo_labels (csrc/eval.hip) on device tensors."""
+    return _make_labels(batch, vr_thres, None, "make_labels")
 
 
 def make_labels_ragged(batch, vr_thres):
@@ -45,22 +53,9 @@ def make_labels_ragged(batch, vr_thres):
     bit-identical to make_labels on the truncated sample at B = 1 (the one reduction over a sample, the mean residual of
     main_util.py:260, runs over its valid points); padded slots of both outputs are 0."""
     pc1, n1 = batch["pc1"], batch["n1"]
-    B, _, N = pc1.shape
-    if n1.dtype != torch.int32 or n1.shape != (B,) or n1.device != pc1.device:
+    if n1.dtype != torch.int32 or n1.shape != (pc1.shape[0],) or n1.device != pc1.device:
         raise ValueError("make_labels_ragged: n1 is a (B,) int32 tensor on the inputs' device")
-    if not pc1.is_cuda:
-        raise RuntimeError("cmflow_amd.losses.make_labels_ragged runs on the GPU only (got %s tensors)" % pc1.device)
-    f32 = torch.float32
-    c = lambda t: t.to(f32).contiguous()
-    pc, T, vel, dt = c(pc1), c(batch["gt_trans"]), c(batch["ft1"][:, 0]), c(batch["interval"])
-    fg, fl = c(batch["fg_mask"]), c(batch["flow_label"])
-    dyn_mask, mseg_gt = torch.empty(B, N, dtype=f32, device=pc1.device), torch.empty(B, N, dtype=f32, device=pc1.device)
-    p = lambda t: _lib.dev_ptr(t, f32)
-    _lib.check(_lib.lib().cmf_pseudo_labels_counted(B, N, _lib.dev_ptr(n1.contiguous(), torch.int32), p(pc), p(T), p(vel), p(dt),
-                                                    p(fg), p(fl), vr_thres, p(dyn_mask), p(mseg_gt), None, _lib.stream_ptr()),
-               "cmf_pseudo_labels_counted")
-    return dyn_mask.to(batch["fg_mask"].dtype), mseg_gt
-
+    return _make_labels(batch, vr_thres, n1, "make_labels_ragged")
 
 
 MAX_N = 65536                                # include/cmflow_hip.h CMF_RADAR_LOSS_MAX_N

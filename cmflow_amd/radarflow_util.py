@@ -48,58 +48,76 @@ def index_points_group(points, knn_idx):
     return group_rows(points, Neighbors(knn_idx.int().contiguous(), points.shape[1]))
 
 
-def knn_point(nsample, xyz, new_xyz, return_dist=False, i32=False):
-    """radarflow_util.py:88-99: xyz (B,N,3) database, new_xyz (B,S,3) queries -> (B,S,nsample)
-    int64 (torch.topk's dtype; i32=True: the kernel's own int32 tensor, for the blocks).  Order is canonical (ascending distance,
-    lowest index first); the reference's topk(sorted=False) order is unspecified."""
+def _knn(nsample, xyz, new_xyz, n_src, return_dist):
+    """cmf_knn (n_src None) / cmf_knn_counted -> idx (B,S,nsample) int32, dist (B,S,nsample) or None"""
     xyz = xyz.detach().contiguous()
     new_xyz = new_xyz.detach().contiguous()
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
     idx = torch.empty(B, S, nsample, dtype=_i32, device=xyz.device)
     dist = torch.empty(B, S, nsample, dtype=_f32, device=xyz.device) if return_dist else None
-    err = _lib.lib().cmf_knn(B, N, S, nsample, _lib.dev_ptr(xyz, _f32), _lib.dev_ptr(new_xyz, _f32),
-                             _lib.dev_ptr(idx, _i32), _lib.dev_ptr(dist, _f32), _lib.stream_ptr())
-    _lib.check(err, "cmf_knn")
-    if i32:
-        return (idx, dist) if return_dist else idx
-    return (idx.long(), dist) if return_dist else idx.long()
+    name = "cmf_knn" if n_src is None else "cmf_knn_counted"
+    counts = () if n_src is None else (_lib.dev_ptr(n_src, _i32),)
+    err = getattr(_lib.lib(), name)(B, N, S, nsample, _lib.dev_ptr(xyz, _f32), _lib.dev_ptr(new_xyz, _f32), *counts,
+                                    _lib.dev_ptr(idx, _i32), _lib.dev_ptr(dist, _f32), _lib.stream_ptr())
+    _lib.check(err, name)
+    return idx, dist
+
+
+def knn_point(nsample, xyz, new_xyz, return_dist=False, i32=False):
+    """radarflow_util.py:88-99: xyz (B,N,3) database, new_xyz (B,S,3) queries -> (B,S,nsample)
+    int64 (torch.topk's dtype; i32=True: the kernel's own int32 tensor, for the blocks).  Order is canonical (ascending distance,
+    lowest index first); the reference's topk(sorted=False) order is unspecified."""
+    idx, dist = _knn(nsample, xyz, new_xyz, None, return_dist)
+    if not i32:
+        idx = idx.long()
+    return (idx, dist) if return_dist else idx
 
 
 def knn_point_counted(nsample, xyz, new_xyz, n_src, return_dist=False):
     """knn_point over RAGGED samples: xyz (B,Nmax,3) padded database with n_src (B,) int32 valid rows per sample, new_xyz (B,S,3)
     -> (B,S,nsample) int32, canonical order, candidates below the sample's count only (cmf_knn_counted)."""
-    xyz = xyz.detach().contiguous()
-    new_xyz = new_xyz.detach().contiguous()
-    B, N, _ = xyz.shape
-    S = new_xyz.shape[1]
-    idx = torch.empty(B, S, nsample, dtype=_i32, device=xyz.device)
-    dist = torch.empty(B, S, nsample, dtype=_f32, device=xyz.device) if return_dist else None
-    err = _lib.lib().cmf_knn_counted(B, N, S, nsample, _lib.dev_ptr(xyz, _f32), _lib.dev_ptr(new_xyz, _f32), _lib.dev_ptr(n_src, _i32),
-                                     _lib.dev_ptr(idx, _i32), _lib.dev_ptr(dist, _f32), _lib.stream_ptr())
-    _lib.check(err, "cmf_knn_counted")
+    if n_src is None:
+        raise RuntimeError("cmf_knn_counted failed: no per-sample counts")
+    idx, dist = _knn(nsample, xyz, new_xyz, n_src, return_dist)
     return (idx, dist) if return_dist else idx
+
+
+def _ego_refine_launch(flow, pc1, score, counts, eps, thres, want_aux):
+    """cmf_ego_refine (counts None) / cmf_ego_refine_counted -> the contiguous inputs and every buffer of the call:
+    (pc1, score, W, Bm, trans, aux, sf, mask uint8, stat).  aux: the solve's record for the backward pass (None unless want_aux);
+    stat: counted only."""
+    flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
+    b, _, n = pc1.shape
+    dev = pc1.device
+    W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
+    trans = torch.empty(b, 4, 4, dtype=_f32, device=dev)
+    aux = torch.empty(b, 32, dtype=torch.float64, device=dev) if want_aux else None
+    sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
+    head = (b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32), _lib.dev_ptr(score, _f32))
+    out = (_lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32), _lib.dev_ptr(trans, _f32), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(sf, _f32),
+           mask.data_ptr())
+    if counts is None:
+        stat = None
+        _lib.check(_lib.lib().cmf_ego_refine(*head, *out, _lib.stream_ptr()), "cmf_ego_refine")
+    else:
+        stat = torch.empty(b, n, dtype=_f32, device=dev)
+        _lib.check(_lib.lib().cmf_ego_refine_counted(*head, _lib.dev_ptr(counts, _i32), *out, _lib.dev_ptr(stat, _f32), _lib.stream_ptr()),
+                   "cmf_ego_refine_counted")
+    return pc1, score, W, Bm, trans, aux, sf, mask, stat
 
 
 def ego_refine_counted(flow, pc1, score, counts, eps, thres):
     """ego_refine over RAGGED samples: flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
     (pre_trans (b,4,4), sf_agg (b,3,Nmax), mask (b,Nmax) bool, stat (b,Nmax)): the solve over each sample's valid points
     (cmf_ego_refine_counted: bit-identical to the dense call on the truncated sample); padded slots: flow 0, mask False, stat 0.
-    With autograd recording and an input that needs a gradient this is the _EgoRefineCounted node (stat carries no gradient)."""
+    With autograd recording and an input that needs a gradient this is the _EgoRefine node (stat carries no gradient); otherwise
+    the solve's aux record is neither allocated nor written."""
+    if counts is None:
+        raise RuntimeError("cmf_ego_refine_counted failed: no per-sample counts")
     if torch.is_grad_enabled() and (flow.requires_grad or score.requires_grad):
-        return _EgoRefineCounted.apply(flow, pc1, score, counts, eps, thres)
-    flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
-    b, _, n = pc1.shape
-    dev = pc1.device
-    W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
-    trans = torch.empty(b, 4, 4, dtype=_f32, device=dev)
-    sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
-    stat = torch.empty(b, n, dtype=_f32, device=dev)
-    err = _lib.lib().cmf_ego_refine_counted(b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32),
-                                            _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32),
-                                            _lib.dev_ptr(trans, _f32), None, _lib.dev_ptr(sf, _f32), mask.data_ptr(), _lib.dev_ptr(stat, _f32),
-                                            _lib.stream_ptr())
-    _lib.check(err, "cmf_ego_refine_counted")
+        return _EgoRefine.apply(flow, pc1, score, counts, eps, thres)
+    _, _, _, _, trans, _, sf, mask, stat = _ego_refine_launch(flow, pc1, score, counts, eps, thres, False)
     return trans, sf, mask.view(torch.bool), stat
 
 
@@ -153,89 +171,46 @@ def weighted_kabsch(A, B, W):
 
 class _EgoRefine(Function):
     """EgoMotionHead + refine_with_transform (models/cmflow.py:96-125) as one native call per direction (cmf_ego_refine):
-    flow (b,3,N), pc1 (b,3,N), score (b,N) -> pre_trans (b,4,4), sf_agg (b,3,N), mask (b,N) bool.  pc1 takes no gradient."""
-
-    @staticmethod
-    def forward(ctx, flow, pc1, score, eps, thres):
-        flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
-        b, _, n = pc1.shape
-        dev = pc1.device
-        W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
-        trans = torch.empty(b, 4, 4, dtype=_f32, device=dev); aux = torch.empty(b, 32, dtype=torch.float64, device=dev)
-        sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
-        err = _lib.lib().cmf_ego_refine(b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32),
-                                        _lib.dev_ptr(score, _f32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32), _lib.dev_ptr(trans, _f32),
-                                        _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(sf, _f32), mask.data_ptr(), _lib.stream_ptr())
-        _lib.check(err, "cmf_ego_refine")
-        ctx.save_for_backward(pc1, score, W, Bm, mask, aux)
-        ctx.eps = float(eps)
-        mask_b = mask.view(torch.bool)
-        ctx.mark_non_differentiable(mask_b)
-        return trans, sf, mask_b
-
-    @staticmethod
-    def backward(ctx, g_trans, g_sf, _g_mask):
-        pc1, score, W, Bm, mask, aux = ctx.saved_tensors
-        b, _, n = pc1.shape
-        if g_sf is None:
-            g_sf = torch.zeros_like(Bm)
-        g_flow = torch.empty_like(Bm); g_w = torch.empty_like(W)
-        g_score = torch.empty_like(W) if ctx.needs_input_grad[2] else None
-        err = _lib.lib().cmf_ego_refine_grad(
-            b, n, ctx.eps, _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(score, _f32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32), mask.data_ptr(),
-            _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(g_sf.contiguous(), _f32),
-            _lib.dev_ptr(g_trans.contiguous(), _f32) if g_trans is not None else None,
-            _lib.dev_ptr(g_flow, _f32), _lib.dev_ptr(g_w, _f32), _lib.dev_ptr(g_score, _f32), _lib.stream_ptr())
-        _lib.check(err, "cmf_ego_refine_grad")
-        return g_flow, None, g_score, None, None
-
-
-class _EgoRefineCounted(Function):
-    """_EgoRefine over RAGGED samples (training under eval-mode BatchNorm): flow, pc1 (b,3,Nmax), score (b,Nmax), counts (b,) int32 ->
-    pre_trans, sf_agg, mask, stat as ego_refine_counted returns them, with the solve's aux record kept; backward is
-    cmf_ego_refine_grad_counted -- the valid slices of the gradients equal the dense node's on the truncated sample bit for bit and
-    the padded slots are zeros whatever the incoming gradient holds there."""
+    flow (b,3,N), pc1 (b,3,N), score (b,N) -> pre_trans (b,4,4), sf_agg (b,3,N), mask (b,N) bool.  pc1 takes no gradient.
+    counts (b,) int32 instead of None: RAGGED samples (training under eval-mode BatchNorm) of Nmax = N padded rows; the outputs are
+    ego_refine_counted's, stat (b,N) behind the mask, and backward is cmf_ego_refine_grad_counted -- the valid slices of the gradients
+    equal the dense node's on the truncated sample bit for bit and the padded slots are zeros whatever the incoming gradient holds
+    there."""
 
     @staticmethod
     def forward(ctx, flow, pc1, score, counts, eps, thres):
-        flow, pc1, score = flow.contiguous(), pc1.contiguous(), score.contiguous()
-        b, _, n = pc1.shape
-        dev = pc1.device
-        W = torch.empty(b, n, dtype=_f32, device=dev); Bm = torch.empty(b, 3, n, dtype=_f32, device=dev)
-        trans = torch.empty(b, 4, 4, dtype=_f32, device=dev); aux = torch.empty(b, 32, dtype=torch.float64, device=dev)
-        sf = torch.empty(b, 3, n, dtype=_f32, device=dev); mask = torch.empty(b, n, dtype=torch.uint8, device=dev)
-        stat = torch.empty(b, n, dtype=_f32, device=dev)
-        err = _lib.lib().cmf_ego_refine_counted(b, n, float(eps), float(thres), _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(flow, _f32),
-                                                _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32),
-                                                _lib.dev_ptr(trans, _f32), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(sf, _f32),
-                                                mask.data_ptr(), _lib.dev_ptr(stat, _f32), _lib.stream_ptr())
-        _lib.check(err, "cmf_ego_refine_counted")
+        pc1, score, W, Bm, trans, aux, sf, mask, stat = _ego_refine_launch(flow, pc1, score, counts, eps, thres, True)
         ctx.save_for_backward(pc1, score, W, Bm, mask, aux, counts)
         ctx.eps = float(eps)
         mask_b = mask.view(torch.bool)
+        if counts is None:
+            ctx.mark_non_differentiable(mask_b)
+            return trans, sf, mask_b
         ctx.mark_non_differentiable(mask_b, stat)
         return trans, sf, mask_b, stat
 
     @staticmethod
-    def backward(ctx, g_trans, g_sf, _g_mask, _g_stat):
+    def backward(ctx, g_trans, g_sf, *_g_mask_stat):
         pc1, score, W, Bm, mask, aux, counts = ctx.saved_tensors
         b, _, n = pc1.shape
         if g_sf is None:
             g_sf = torch.zeros_like(Bm)
         g_flow = torch.empty_like(Bm); g_w = torch.empty_like(W)
         g_score = torch.empty_like(W) if ctx.needs_input_grad[2] else None
-        err = _lib.lib().cmf_ego_refine_grad_counted(
-            b, n, ctx.eps, _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(score, _f32), _lib.dev_ptr(counts, _i32), _lib.dev_ptr(W, _f32),
-            _lib.dev_ptr(Bm, _f32), mask.data_ptr(), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(g_sf.contiguous(), _f32),
+        name = "cmf_ego_refine_grad" if counts is None else "cmf_ego_refine_grad_counted"
+        cnt = () if counts is None else (_lib.dev_ptr(counts, _i32),)
+        err = getattr(_lib.lib(), name)(
+            b, n, ctx.eps, _lib.dev_ptr(pc1, _f32), _lib.dev_ptr(score, _f32), *cnt, _lib.dev_ptr(W, _f32), _lib.dev_ptr(Bm, _f32),
+            mask.data_ptr(), _lib.dev_ptr(aux, torch.float64), _lib.dev_ptr(g_sf.contiguous(), _f32),
             _lib.dev_ptr(g_trans.contiguous(), _f32) if g_trans is not None else None,
             _lib.dev_ptr(g_flow, _f32), _lib.dev_ptr(g_w, _f32), _lib.dev_ptr(g_score, _f32), _lib.stream_ptr())
-        _lib.check(err, "cmf_ego_refine_grad_counted")
+        _lib.check(err, name)
         return g_flow, None, g_score, None, None, None
 
 
 def ego_refine(flow, pc1, score, eps, thres):
     """-> (pre_trans, sf_agg, mask): cmflow.py:96-125 with score (b,N) the (detached label or predicted) motion scores."""
-    return _EgoRefine.apply(flow, pc1, score, eps, thres)
+    return _EgoRefine.apply(flow, pc1, score, None, eps, thres)
 
 
 def _rows(t, pad4=False):

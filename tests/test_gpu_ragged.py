@@ -38,7 +38,7 @@ def _pad_fill(t, counts, fill, seed=0):
     g = torch.Generator().manual_seed(seed)
     for i, c in enumerate(counts):
         n = t.shape[1] - c
-        if n == 0:
+        if n == 0 or (c == 0 and fill == "copies"):                 # nothing to pad / no valid row to copy: the rows stay as drawn
             continue
         if fill == "big":
             sign = (torch.randint(0, 2, (n, *t.shape[2:]), generator=g) * 2 - 1).to(t.dtype)
@@ -53,34 +53,50 @@ def _cloud(B, N, seed):
     return b["pc1"].transpose(1, 2).contiguous(), b["pc2"].transpose(1, 2).contiguous()      # (B,N,3)
 
 
+# padded sizes of the nested ball query: NMAX with COUNTS, and the edges of the kernel's chunk-count ladder (n <= 256: 1 chunk,
+# <= 512: 2, else 4) with a full sample, one row short of it, a sample WITHOUT centres (a wave with no live centre skips the cloud),
+# and odd counts: a wave serves G = 2 consecutive centres at these shapes, so an odd count ends inside a wave's group
+BQ_CASES = ((NMAX, COUNTS),) + tuple((n, (n, n - 1, 211, 8, 1, 0, 97)) for n in (256, 257, 513))
+
+
 @pytest.mark.parametrize("fill", FILLS)
 def test_counted_nested_ball_query_is_bit_exact(dev, fill):
     """All four (radius, nsample) pairs, two clouds in one launch: every valid centre's list == cmf_ball_query on the truncated
-    sample; padded centres write zero rows."""
+    sample; padded centres write zero rows.  Every chunk-count instantiation of the kernel (BQ_CASES)."""
     from cmflow_amd import _lib
-    B = len(COUNTS)
-    x1, x2 = _cloud(B, NMAX, 11)
-    c1, c2 = COUNTS, COUNTS[::-1]
-    x1, x2 = _pad_fill(x1, c1, fill).to(dev), _pad_fill(x2, c2, fill, 1).to(dev)
-    n1, n2 = torch.tensor(c1, dtype=_i32, device=dev), torch.tensor(c2, dtype=_i32, device=dev)
-    idx = [[torch.full((B, NMAX, s), -7, dtype=_i32, device=dev) for s in NSAMPLES] for _ in range(2)]
-    radii = (ctypes.c_float * 4)(*RADII)
-    ns = (ctypes.c_int * 4)(*NSAMPLES)
-    cl = (ctypes.c_void_p * 2)(x1.data_ptr(), x2.data_ptr())
-    ip = (ctypes.c_void_p * 8)(*[t.data_ptr() for c in idx for t in c])
-    cn = (ctypes.c_void_p * 2)(n1.data_ptr(), n2.data_ptr())
-    _lib.check(_lib.lib().cmf_ball_query_multi_counted(B, NMAX, NMAX, 4, ctypes.addressof(radii), ctypes.addressof(ns), 2, ctypes.addressof(cl),
-                                                       ctypes.addressof(cl), ctypes.addressof(ip), ctypes.addressof(cn), ctypes.addressof(cn),
-                                                       _lib.stream_ptr()), "cmf_ball_query_multi_counted")
-    for c, (x, counts) in enumerate(((x1, c1), (x2, c2))):
-        for q, (r, s) in enumerate(zip(RADII, NSAMPLES)):
-            for i, n in enumerate(counts):
-                xs = x[i:i + 1, :n].contiguous()
-                want = torch.zeros(1, n, s, dtype=_i32, device=dev)
-                _lib.check(_lib.lib().cmf_ball_query(1, n, n, r, s, xs.data_ptr(), xs.data_ptr(), want.data_ptr(), _lib.stream_ptr()), "cmf_ball_query")
-                assert torch.equal(idx[c][q][i, :n], want[0]), (c, q, i, n)
-                assert int(idx[c][q][i, :n].max()) < n
-                assert not idx[c][q][i, n:].any(), (c, q, i, n)
+    for nmax, c1 in BQ_CASES:
+        B = len(c1)
+        x1, x2 = _cloud(B, nmax, 11)
+        c2 = c1[::-1]
+        x1, x2 = _pad_fill(x1, c1, fill).to(dev), _pad_fill(x2, c2, fill, 1).to(dev)
+        n1, n2 = torch.tensor(c1, dtype=_i32, device=dev), torch.tensor(c2, dtype=_i32, device=dev)
+        idx = [[torch.full((B, nmax, s), -7, dtype=_i32, device=dev) for s in NSAMPLES] for _ in range(2)]
+        radii = (ctypes.c_float * 4)(*RADII)
+        ns = (ctypes.c_int * 4)(*NSAMPLES)
+        cl = (ctypes.c_void_p * 2)(x1.data_ptr(), x2.data_ptr())
+        ip = (ctypes.c_void_p * 8)(*[t.data_ptr() for c in idx for t in c])
+        cn = (ctypes.c_void_p * 2)(n1.data_ptr(), n2.data_ptr())
+        _lib.check(_lib.lib().cmf_ball_query_multi_counted(B, nmax, nmax, 4, ctypes.addressof(radii), ctypes.addressof(ns), 2, ctypes.addressof(cl),
+                                                           ctypes.addressof(cl), ctypes.addressof(ip), ctypes.addressof(cn), ctypes.addressof(cn),
+                                                           _lib.stream_ptr()), "cmf_ball_query_multi_counted")
+        for c, (x, counts) in enumerate(((x1, c1), (x2, c2))):
+            for q, (r, s) in enumerate(zip(RADII, NSAMPLES)):
+                for i, n in enumerate(counts):
+                    assert not idx[c][q][i, n:].any(), (nmax, c, q, i, n)
+                    if n == 0:
+                        continue
+                    xs = x[i:i + 1, :n].contiguous()
+                    want = torch.zeros(1, n, s, dtype=_i32, device=dev)
+                    _lib.check(_lib.lib().cmf_ball_query(1, n, n, r, s, xs.data_ptr(), xs.data_ptr(), want.data_ptr(), _lib.stream_ptr()), "cmf_ball_query")
+                    assert torch.equal(idx[c][q][i, :n], want[0]), (nmax, c, q, i, n)
+                    assert int(idx[c][q][i, :n].max()) < n
+
+
+# the list-length ladder of the kNN launcher (K = 1, 4, 8, 16, 32) over one padded database of 1100 rows: past the kernel's LDS tile
+# (1024 points), one row past it, exactly the tile, a single point (shorter than every list but the first) and an empty sample;
+# 70 queries per sample: one full and one partial wave
+KNN_NSAMPLES = (1, 4, 8, 16, 32)
+KNN_NMAX, KNN_COUNTS, KNN_QUERIES = 1100, (1100, 1025, 1024, 1, 0), 70
 
 
 @pytest.mark.parametrize("fill", FILLS)
@@ -97,6 +113,20 @@ def test_counted_knn_is_bit_exact(dev, fill):
         assert torch.equal(got[i, :a], want[0]), i
         assert torch.equal(gd[i, :a].view(_i32), wd[0].view(_i32)), i
         assert int(got[i].max()) < b                                 # padded queries too: valid rows of their own sample
+    # every rung of the ladder, the tile edge, and the counts below a list's length
+    qs, db = _cloud(len(KNN_COUNTS), KNN_NMAX, 13)
+    qs, db = qs[:, :KNN_QUERIES].contiguous().to(dev), _pad_fill(db, KNN_COUNTS, fill, 2).to(dev)
+    cnt = torch.tensor(KNN_COUNTS, dtype=_i32, device=dev)
+    for ns in KNN_NSAMPLES:
+        got, gd = knn_point_counted(ns, db, qs, cnt, return_dist=True)
+        assert got.dtype == _i32 and got.shape == gd.shape == (len(KNN_COUNTS), KNN_QUERIES, ns)
+        for i, n in enumerate(KNN_COUNTS):
+            if n == 0:                                               # as the dense kernel answers n = 0: index 0, distance 0
+                assert not got[i].any() and not gd[i].view(_i32).any(), (ns, i)
+                continue
+            want, wd = knn_point(ns, db[i:i + 1, :n].contiguous(), qs[i:i + 1], return_dist=True, i32=True)
+            assert torch.equal(got[i], want[0]), (ns, i, n)
+            assert torch.equal(gd[i].view(_i32), wd[0].view(_i32)), (ns, i, n)
 
 
 @pytest.mark.parametrize("fill", FILLS)

@@ -116,10 +116,11 @@ def test_counted_neighbour_kernels_follow_the_isa_rule():
                           "--cuda-device-only", "-o", "-", src], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     asm = out.stdout
-    for sym in ("_Z31ball_query_multi_counted_kernelILi1E", "_Z31ball_query_multi_counted_kernelILi2E", "_Z31ball_query_multi_counted_kernelILi4E"):
+    for sym in ("_Z30ball_query_multi_ballot_kernelILi1ELb1E", "_Z30ball_query_multi_ballot_kernelILi2ELb1E",
+                "_Z30ball_query_multi_ballot_kernelILi4ELb1E"):
         start = asm.index(sym + "Ev")
         body = asm[start:asm.index("s_endpgm", start)]
         assert not re.search(r"v_(fma|fmac|mad|pk_fma)_f32", body), sym
-    knn = asm[asm.index("_Z18knn_counted_kernelILi8EEv"):]
+    knn = asm[asm.index("_Z10knn_kernelILi8ELb0ELb1EEv"):]
     knn = knn[:knn.index("s_endpgm")]
     assert re.search(r"v_(fma|fmac)_f32", knn)
