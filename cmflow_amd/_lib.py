@@ -164,6 +164,9 @@ SIGNATURES = {
     "cmf_vis_render_bev": [_ci, _ci, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _cf, _cf, _cf, _ci, _vp, _vp],
     # a test run's clouds accumulated over a window of frames (accumulate.py)
     "cmf_accumulate": [_ci, _ci, _vp, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _ll, _vp, _vp, _vp, _vp, _vp],
+    # moving-object instances of a test run (instances.py)
+    "cmf_cluster_moving": [_ci, _ci, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _vp, _ci, ctypes.c_double, ctypes.c_double, _ci,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

@@ -254,6 +254,12 @@ class SplitResults:
         from . import accumulate as A
         return A.accumulate(split, self, window=window, which=which, dynamic=dynamic, frames=frames)
 
+    def instances(self, split, **kw):
+        """``instances.cluster(split, self, ...)``: the moving points of every selected frame grouped into instances (``which``,
+        ``eps``, ``min_points``, ``flow_weight``, ``frames`` as there)."""
+        from . import instances as I
+        return I.cluster(split, self, **kw)
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

@@ -195,6 +195,62 @@ def render_accumulated(acc, store, split, layer, view=None):
     return out
 
 
+# the instances of ``instances.cluster``: twelve colours by label % 12, light grey for noise, dim grey for a point that is no candidate
+INSTANCE_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180),
+                    (70, 240, 240), (240, 50, 230), (210, 245, 60), (250, 190, 212), (0, 128, 128), (170, 110, 40))
+INSTANCE_NOISE, INSTANCE_STATIC = (200, 200, 200), (120, 120, 120)
+
+
+def instance_colors(label, kind):
+    """The colours of ``render_instances``, (n, 3) uint8 from ``label`` (n) int32 and ``kind`` (n) uint8 on any device, in whole
+    numbers: a core or border point (kind >= 2) gets entry ``label % 12`` of ``INSTANCE_PALETTE``, a noise point (kind 1) light grey
+    (200, 200, 200), every other point dim grey (120, 120, 120)."""
+    slot = torch.remainder(label.to(torch.int32), len(INSTANCE_PALETTE))
+    member, noise = kind >= 2, kind == 1
+    channels = []
+    for ch in range(3):
+        col = torch.full_like(slot, INSTANCE_STATIC[ch])
+        col = torch.where(noise, torch.full_like(slot, INSTANCE_NOISE[ch]), col)
+        for k, rgb in enumerate(INSTANCE_PALETTE):
+            col = torch.where(member & (slot == k), torch.full_like(slot, rgb[ch]), col)
+        channels.append(col)
+    return torch.stack(channels, dim=1).to(torch.uint8)
+
+
+def render_instances(inst, split, frames=None, view=None):
+    """Bird's-eye-view pictures of clustered frames (``instances.cluster``) -> (frames, H, W, 3) uint8 on the device.  ``frames``:
+    None (the frames ``inst`` was computed for), a list, or an int64 tensor; a frame ``inst`` does not hold is drawn dim grey.  Every
+    point of a selected frame is drawn in its ``instance_colors``, in index order.  ``view`` as ``render``.  A few whole-number torch
+    ops and ONE call of the rasteriser ``render`` uses (``cmf_vis_render_bev``); the host never waits."""
+    if len(split) != inst.off.numel() - 1 or split.tab1.shape[0] != inst.label.shape[0]:
+        raise ValueError("vis.render_instances: the split is not the one these instances belong to")
+    if not (inst.label.is_cuda and split.tab1.is_cuda and inst.label.device == split.tab1.device):
+        raise RuntimeError("vis.render_instances: instances on %s, split on %s; pictures are rendered on the GPU only (no CPU fallback)"
+                           % (inst.label.device, split.tab1.device))
+    view = BevView() if view is None else view
+    if frames is None:
+        sel, nsel = (None, len(split)) if inst.frames_host.size == len(split) and bool((inst.frames_host == np.arange(len(split))).all()) \
+            else (inst.frames, len(inst))
+    else:
+        sel, nsel = _selection(split, frames, "vis.render_instances")
+    if nsel > MAX_FRAMES:
+        raise ValueError("vis.render_instances: %d frames in one call (at most %d)" % (nsel, MAX_FRAMES))
+    total, u8 = inst.label.shape[0], torch.uint8
+    out = torch.empty((nsel, view.height, view.width, 3), dtype=u8, device=inst.device)
+    if nsel == 0:
+        return out
+    colors = instance_colors(inst.label, inst.kind).contiguous()
+    drawn = torch.ones((total,), dtype=u8, device=inst.device)
+    p = {k: float(v) for k, v in view.kernel_params().items()}
+    with torch.cuda.device(inst.device):
+        _lib.check(_lib.lib().cmf_vis_render_bev(
+            nsel, len(split), None if sel is None else _lib.dev_ptr(sel, torch.int64), _lib.dev_ptr(split.off1, torch.int32), total,
+            _lib.dev_ptr(split.tab1, torch.float32), split.tab1.shape[1], _lib.dev_ptr(colors, u8), _lib.dev_ptr(drawn, u8),
+            view.width, view.height, p["x0"], p["y1"], p["s"], p["inv_s"], p["half"], p["radius"], p["r2"], int(view.guides),
+            _lib.dev_ptr(out, u8), _lib.stream_ptr()), "cmf_vis_render_bev")
+    return out
+
+
 # ---- PNG, with the stdlib only ----------------------------------------------------------------------------------------------------------
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
 

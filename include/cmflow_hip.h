@@ -1116,6 +1116,55 @@ int cmf_accumulate(int nsel, int nframes, const long long *frames, const int *fi
                    int mode, int gt, const int *cap_off, long long cap_total, float *xyz, int *src, unsigned char *age,
                    int *count, void *stream);
 
+/* ---- moving-object instances of a test run (cmflow_amd/instances.py) ---------------------------------------------
+ * cmf_cluster_moving: density-based clustering (DBSCAN with its one order-dependent choice pinned) of the moving cloud-1 points of
+ * every selected frame, each frame on its own -- a definition, not an approximation of one.
+ *   frames (nsel) int64 in device memory, ids clamped to [0, nframes-1], the same id may occur twice; NULL: frames 0 .. nsel-1.
+ *   off1 / total / tab1 / ld_tab: the split's cloud-1 table (xyz at columns 0..2, label flow 6..8, mask 9; ld_tab >= 10).
+ *   gt == 0: flow (total,3) and mask (total) bytes are the store's, T (nframes,16) its trans_pred; a point is a CANDIDATE iff its
+ *            mask byte is 0.
+ *   gt != 0: flow and mask are not read (may be NULL); the flow is tab1's columns 6..8, a point is a candidate iff tab1 column 9
+ *            == 0.0f, and T is the split's trans.
+ *   eps2 = (double)eps * (double)eps, w2 = (double)flow_weight * (double)flow_weight, formed by the host; min_points >= 1.
+ * For a frame with n points, p_i its float32 positions, f_i the flow and T the frame's transform, a point's own-motion
+ * displacement is cmf_accumulate's d, expression for expression:
+ *     tp_r = ((T[r][0] px + T[r][1] py) + T[r][2] pz) + T[r][3]         d_r = ((double)p_r + (double)f_r) - tp_r
+ * and for two candidates i, j, with dx.. = (double)p_i - (double)p_j and ex.. = d_i - d_j:
+ *     D2(i,j) = ((dx*dx + dy*dy) + dz*dz) + w2 * ((ex*ex + ey*ey) + ez*ez)
+ * All float64, every operation rounded on its own (no contraction).  w2 = 0 clusters by position alone (for finite d).
+ *   Neighbours: candidates i, j with D2(i,j) <= eps2; a point is its own neighbour (a NaN distance is no neighbour, not even of itself).
+ *   Core:       a candidate with at least min_points neighbours, itself included.
+ *   Instances:  the connected components of the core points under the neighbour relation.
+ *   Border:     a candidate that is not core but has a core neighbour; it joins the instance of the core neighbour with the smallest
+ *               D2, the lowest point index among equal D2 -- the one place where textbook DBSCAN depends on the visiting order.
+ *   Noise:      any other candidate.
+ *   Numbering:  a frame's instances are 0 .. K-1 in ascending order of their lowest-indexed core point, the instance's seed.
+ *   Statistics of an instance over its members (core and border) in ascending point index: size; centroid_r = (float)(S_r /
+ *               (double)size) with S_r the float64 sum of (double)p_r in that order from 0.0; disp_r likewise from d_r; lo_r, hi_r
+ *               the smallest and largest float32 coordinate (from the first member, replaced only where v < lo_r, v > hi_r); seed.
+ * Outputs, packed like the cloud-1 table: label (total) int32, the instance id inside the frame or -1; kind (total) bytes,
+ *   CMF_INST_NONE (no candidate), _NOISE, _BORDER, _CORE; count (nframes) int32, the K of frame f at count[f].  The instance tables share
+ *   the points' row space -- instance c of frame f is row off1[f] + c, K <= n always: size, seed (total) int32, seed the frame-local
+ *   point index; centroid, disp, lo, hi (total,3) float32.
+ * Guarantees, as cmf_accumulate: every label, kind and table row of a selected frame is written, by the one thread that owns it (no
+ *   atomics, no global scratch); table rows behind K hold size 0, seed -1 and zeros; rows of unselected frames are not touched; the
+ *   same id selected twice writes the same values twice.  A frame with more than CMF_INST_MAX_POINTS points has no candidates (count
+ *   0, labels -1, kind 0, empty table rows); a frame whose rows do not lie inside [0, total) owns no rows and gets count 0: a bad id or
+ *   offset gives wrong data, never an access outside a buffer.  total <= INT_MAX.
+ *   One workgroup per selected frame, one thread per candidate, the candidates in 52 KB of LDS; every pair distance is formed once
+ *   (a thread keeps its row of the neighbour relation as bits in registers); the components are the fixed point "every core point
+ *   carries the lowest core index of its component", reached by rounds that read only what the round before wrote, so the result
+ *   does not depend on the schedule.  tests/instances_ref.py restates all of this in numpy, bit for bit. */
+#define CMF_INST_MAX_POINTS 1024
+#define CMF_INST_NONE 0
+#define CMF_INST_NOISE 1
+#define CMF_INST_BORDER 2
+#define CMF_INST_CORE 3
+int cmf_cluster_moving(int nsel, int nframes, const long long *frames, const int *off1, long long total, const float *tab1,
+                       int ld_tab, const float *flow, const unsigned char *mask, const float *T, int gt, double eps2, double w2,
+                       int min_points, int *label, unsigned char *kind, int *count, int *size, int *seed, float *centroid,
+                       float *disp, float *lo, float *hi, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
