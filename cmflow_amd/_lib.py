@@ -167,6 +167,9 @@ SIGNATURES = {
     # moving-object instances of a test run (instances.py)
     "cmf_cluster_moving": [_ci, _ci, _vp, _vp, _ll, _vp, _ci, _vp, _vp, _vp, _ci, ctypes.c_double, ctypes.c_double, _ci,
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # the instances tracked across a clip's frames (tracks.py)
+    "cmf_track_instances": [_ci, _ci, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _ci,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

@@ -9,9 +9,9 @@ position and, weighted by ``flow_weight``, by the displacement they show against
 DBSCAN pinned (a border point joins its nearest core neighbour, the lowest index among equals), stated in include/cmflow_hip.h and
 DESIGN.md section 22 and restated in numpy, bit for bit, by tests/instances_ref.py.  ``vis.render_instances`` draws the result.
 
-What this is NOT: there is no tracking across frames (every frame is clustered on its own, and instance 3 of one frame has nothing
-to do with instance 3 of the next), no boxes and no orientation (an instance has a centroid, an axis-aligned extent and a mean
-displacement), no ground-truth object ids (the split has none: ``which='gt'`` clusters the labelled moving points by the same
+What this is NOT: every frame is clustered on its own, so instance 3 of one frame has nothing to do with instance 3 of the next
+(``tracks.track`` associates the instances of a clip's frames and gives an object one id), no boxes and no orientation (an
+instance has a centroid, an axis-aligned extent and a mean displacement), no ground-truth object ids (the split has none: ``which='gt'`` clusters the labelled moving points by the same
 rule, and ``agreement`` compares two clusterings), and nothing is claimed about real data beyond the reference's twelve saved
 frames the tests go through.
 """

@@ -260,6 +260,14 @@ class SplitResults:
         from . import instances as I
         return I.cluster(split, self, **kw)
 
+    def tracks(self, split, inst=None, gate=2.0, max_gap=2, **cluster_kw):
+        """``tracks.track(inst, split, self, gate, max_gap)``: the instances associated from frame to frame inside every clip.  ``inst``:
+        an ``instances`` result of this split, or None -- then ``self.instances(split, **cluster_kw)`` is formed first."""
+        from . import tracks as K
+        if inst is None:
+            inst = self.instances(split, **cluster_kw)
+        return K.track(inst, split, self, gate=gate, max_gap=max_gap)
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

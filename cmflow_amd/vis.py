@@ -222,24 +222,38 @@ def render_instances(inst, split, frames=None, view=None):
     None (the frames ``inst`` was computed for), a list, or an int64 tensor; a frame ``inst`` does not hold is drawn dim grey.  Every
     point of a selected frame is drawn in its ``instance_colors``, in index order.  ``view`` as ``render``.  A few whole-number torch
     ops and ONE call of the rasteriser ``render`` uses (``cmf_vis_render_bev``); the host never waits."""
+    return _render_labelled(inst.label, inst, split, frames, view, "vis.render_instances")
+
+
+def render_tracks(tracks, inst, split, frames=None, view=None):
+    """Bird's-eye-view pictures of tracked frames (``tracks.track``) -> (frames, H, W, 3) uint8 on the device: ``render_instances``
+    with every member point coloured by its TRACK -- ``instance_colors(tracks.point_track, inst.kind)``, entry ``track % 12`` of the
+    palette -- so an object keeps its colour from frame to frame inside a clip (track ids restart with every clip).  ``inst``: the
+    instances ``tracks`` was formed from.  ``frames`` and ``view`` as there; the same ONE call of the rasteriser, the host never waits."""
+    if tracks.point_track.shape != inst.label.shape or tracks.point_track.device != inst.label.device:
+        raise ValueError("vis.render_tracks: the tracks are not the ones of these instances")
+    return _render_labelled(tracks.point_track, inst, split, frames, view, "vis.render_tracks")
+
+
+def _render_labelled(label, inst, split, frames, view, what):
     if len(split) != inst.off.numel() - 1 or split.tab1.shape[0] != inst.label.shape[0]:
-        raise ValueError("vis.render_instances: the split is not the one these instances belong to")
+        raise ValueError("%s: the split is not the one these instances belong to" % what)
     if not (inst.label.is_cuda and split.tab1.is_cuda and inst.label.device == split.tab1.device):
-        raise RuntimeError("vis.render_instances: instances on %s, split on %s; pictures are rendered on the GPU only (no CPU fallback)"
-                           % (inst.label.device, split.tab1.device))
+        raise RuntimeError("%s: instances on %s, split on %s; pictures are rendered on the GPU only (no CPU fallback)"
+                           % (what, inst.label.device, split.tab1.device))
     view = BevView() if view is None else view
     if frames is None:
         sel, nsel = (None, len(split)) if inst.frames_host.size == len(split) and bool((inst.frames_host == np.arange(len(split))).all()) \
             else (inst.frames, len(inst))
     else:
-        sel, nsel = _selection(split, frames, "vis.render_instances")
+        sel, nsel = _selection(split, frames, what)
     if nsel > MAX_FRAMES:
-        raise ValueError("vis.render_instances: %d frames in one call (at most %d)" % (nsel, MAX_FRAMES))
+        raise ValueError("%s: %d frames in one call (at most %d)" % (what, nsel, MAX_FRAMES))
     total, u8 = inst.label.shape[0], torch.uint8
     out = torch.empty((nsel, view.height, view.width, 3), dtype=u8, device=inst.device)
     if nsel == 0:
         return out
-    colors = instance_colors(inst.label, inst.kind).contiguous()
+    colors = instance_colors(label, inst.kind).contiguous()
     drawn = torch.ones((total,), dtype=u8, device=inst.device)
     p = {k: float(v) for k, v in view.kernel_params().items()}
     with torch.cuda.device(inst.device):

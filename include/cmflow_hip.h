@@ -1165,6 +1165,63 @@ int cmf_cluster_moving(int nsel, int nframes, const long long *frames, const int
                        int min_points, int *label, unsigned char *kind, int *count, int *size, int *seed, float *centroid,
                        float *disp, float *lo, float *hi, void *stream);
 
+/* ---- moving-object instances tracked across a clip's frames (cmflow_amd/tracks.py) -------------------------------
+ * cmf_track_instances: the instances of cmf_cluster_moving associated from frame to frame inside every clip, by a gated greedy
+ * nearest-first matching against a constant-displacement prediction -- a definition, not an approximation of one.  Frames of a clip
+ * are consecutive scan pairs (the contract of cmf_pose_chain and cmf_accumulate): T_f maps static points from scan-1 coordinates
+ * of frame f to its scan-2 coordinates, which are the scan-1 coordinates of frame f+1.
+ *   clips (nclips,2) int32 in device memory: [first, last) frame ranges, clamped to [0, nframes] (last < first: empty).
+ *   off1 (nframes+1) / total: the split's cloud-1 offsets; count (nframes), label (total) int32, centroid, disp (total,3) float32:
+ *   cmf_cluster_moving's outputs -- instance c of frame f is row off1[f] + c.  T (nframes,16) float32, row-major: the transforms the
+ *   instances were clustered with.  gate2 = (double)gate * (double)gate, formed by the host; 0 <= max_gap <= CMF_TRACK_MAX_GAP.
+ * Rows.  With base = off1[first], a clip with base outside [0, total] owns no rows.  Its frames are visited in order with top = base
+ *   at the start; frame f OWNS its rows iff top <= off1[f] <= off1[f+1] <= total, and then top = off1[f+1] (so the rows of a clip's
+ *   frames are disjoint and ascend).  A frame that owns no rows has K = 0; otherwise K = count[f] clamped to [0, min(n_f, 1024)].
+ * Per clip the state is the list of live tracks in ascending track id, empty at the clip's first frame; a live track carries
+ *   P (3 float64), its predicted position in the current frame's scan-1 coordinates, D (3 float64), its own-motion displacement per
+ *   frame, and miss, hits, last_row, the frames of its first and last match.  Everything below is float64 from the float32 entries,
+ *   every multiplication and addition rounded on its own (no contraction).  At frame f, with its K instances, c_j the centroid of
+ *   instance j and T = T_f:
+ *   1. Cost:        for a live track and an instance j, e_r = P_r - (double)c_j,r and G2 = (e0 e0 + e1 e1) + e2 e2.  The pair is an
+ *                   EDGE iff G2 <= gate2 (a NaN is no edge).
+ *   2. Association: the edges in ascending (G2, track id, j); an edge MATCHES iff neither of its ends is matched yet.  This order is
+ *                   the definition: it decides every tie.
+ *   3. Matched:     instance j of track u gets track = u, prev_row = the track's last_row, gap = f - (the frame of that match),
+ *                   age = ++hits, pred = (float)P; then P = (double)c_j, D = (double)disp_j, miss = 0, last_row = off1[f] + j.
+ *   4. Births:      the unmatched instances open tracks in ascending j with the clip's next ids: prev_row -1, gap 0, age 1 (hits 1),
+ *                   pred = c_j copied bit for bit; P, D, miss, last_row as in 3.
+ *   5. Unmatched tracks: miss += 1, and the track dies iff miss > max_gap.  A surviving (coasting) track keeps P, and its D is
+ *                   turned into the next frame's axes: D_r := (T[r][0] D_0 + T[r][1] D_1) + T[r][2] D_2.
+ *   6. Capacity:    if matched tracks + coasting tracks + births exceed CMF_TRACK_MAX_LIVE, EVERY coasting track dies at this frame
+ *                   and overflow[clip] += 1 (matched tracks + births = K <= 1024 always fit).
+ *   7. Prediction into frame f+1, for every live track, with D as steps 3-5 left it:
+ *                   P_r := (((T[r][0] P_0 + T[r][1] P_1) + T[r][2] P_2) + T[r][3]) + D_r
+ *                   (disp is (p + flow) - T p, in scan-2 axes already: for a matched instance this is the mean of its points'
+ *                   p + flow, up to rounding).
+ *   8. The live list of frame f+1: the survivors in their old order, then the births -- ascending track id again.
+ *   A frame with K = 0 (count 0, not selected when clustering, or without rows) has no instances: every track coasts.
+ * Outputs in the instances' row space, (total): track, prev_row, gap, age int32, pred (total,3) float32 as above; the rows of an
+ *   owned frame behind K hold track -1, prev_row -1, gap 0, age 0, pred 0.  point_track (total) int32: for point p of an owned frame,
+ *   the track of instance label[p] where 0 <= label[p] < K, else -1.
+ * Outputs in the clip's row space: track u of the clip is row base + u (the tracks of a clip are at most the sum of its K, at most
+ *   its owned rows): birth, last int32, the global frames of its first and last match, hits int32.  The owned rows of the clip from
+ *   base + ntracks on hold -1, -1, 0.  ntracks (nclips), overflow (nclips) int32.
+ * Guarantees, as cmf_cluster_moving: every row of an owned frame is written, by the one thread that owns it (no atomics, no global
+ *   scratch); rows outside every clip are not touched; every row written lies inside [0, total) whatever the offsets, counts, labels
+ *   and clips hold: a bad argument gives wrong data (clips that overlap write the same rows more than once), never an access outside
+ *   a buffer.  total <= INT_MAX.
+ *   One workgroup of 1024 threads per clip, its frames in sequence; thread t owns live slot t (state in registers) and instance t.
+ *   The association runs as mutual-best rounds (a track picks its best unmatched instance by (G2, j), an instance its best unmatched
+ *   track by (G2, track id), pairs that pick each other match) whose fixed point is the sorted greedy matching above; a round reads
+ *   only what the round before wrote, so the result does not depend on the schedule.  The launch keeps nclips CUs busy and lasts as
+ *   long as its longest clip: the state is sequential.  tests/tracks_ref.py restates all of this in numpy, bit for bit. */
+#define CMF_TRACK_MAX_LIVE 1024
+#define CMF_TRACK_MAX_GAP 16
+int cmf_track_instances(int nclips, int nframes, const int *clips, const int *off1, long long total, const int *count,
+                        const int *label, const float *centroid, const float *disp, const float *T, double gate2, int max_gap,
+                        int *track, int *prev_row, int *gap, int *age, float *pred, int *point_track, int *birth, int *last,
+                        int *hits, int *ntracks, int *overflow, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
