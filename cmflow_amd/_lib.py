@@ -170,6 +170,10 @@ SIGNATURES = {
     # the instances tracked across a clip's frames (tracks.py)
     "cmf_track_instances": [_ci, _ci, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _ci,
                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # per-track object states: smoothed kinematics and oriented boxes (objects.py)
+    "cmf_track_states": [_ci, _ci, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp,
+                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

@@ -268,6 +268,18 @@ class SplitResults:
             inst = self.instances(split, **cluster_kw)
         return K.track(inst, split, self, gate=gate, max_gap=max_gap)
 
+    def objects(self, split, trk=None, **kw):
+        """``objects.estimate(trk, split, self, ...)``: per match of every track the smoothed position and velocity, a heading and an
+        oriented box (``sigma_pos``, ``sigma_disp``, ``sigma_acc``, ``min_disp`` as there).  ``trk``: a ``tracks`` result of this
+        split, or None -- then ``self.tracks(split, ...)`` is formed first from the remaining keywords."""
+        from . import objects as O
+        own = {k: kw.pop(k) for k in ("sigma_pos", "sigma_disp", "sigma_acc", "min_disp") if k in kw}
+        if trk is None:
+            trk = self.tracks(split, **kw)
+        elif kw:
+            raise ValueError("SplitResults.objects: %s belong to the tracks, which were given" % ", ".join(sorted(kw)))
+        return O.estimate(trk, split, self, **own)
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

@@ -1222,6 +1222,88 @@ int cmf_track_instances(int nclips, int nframes, const int *clips, const int *of
                         int *track, int *prev_row, int *gap, int *age, float *pred, int *point_track, int *birth, int *last,
                         int *hits, int *ntracks, int *overflow, void *stream);
 
+/* ---- per-track object states: smoothed kinematics and oriented boxes (cmflow_amd/objects.py) ----------------------
+ * cmf_track_states: for every match of every track of cmf_track_instances, the track's position and velocity at that frame from a
+ * fixed-interval smoother over ALL of the track's matches (a constant-velocity Kalman filter forwards, Rauch-Tung-Striebel
+ * backwards), a heading from the smoothed velocity and a box oriented along it -- a definition, not an approximation of one.
+ *   clips, off1, total, count, label, centroid, disp: as cmf_track_instances takes them; track, prev_row, gap (total) int32: its
+ *   outputs.  tab1 / ld_tab: the split's cloud-1 table (xyz at columns 0..2; ld_tab >= 3).  poses (nframes,16) float64: the output of
+ *   cmf_pose_chain on the transforms the instances were clustered with and the SAME clip ranges: A_f = poses[f] is the pose of scan
+ *   2 of frame f in the clip's axes (the scan-1 axes of the clip's first frame); the pose of scan 1 of frame f is W_f = poses[f-1],
+ *   and at the clip's first frame (f == first after clamping) W_f is the identity, taken as the numbers 1.0 and 0.0 through the same
+ *   expressions.  Only the upper three rows of a pose are read.  rp = sigma_pos^2, rd = sigma_disp^2, q = sigma_acc^2,
+ *   min_disp2 = min_disp^2, products of doubles formed by the host (rp, rd > 0; q, min_disp2 >= 0; none NaN).
+ * Rows: the clamping of a clip, base, top, the frames that OWN rows and K_f are those of cmf_track_instances, word for word; row0_f =
+ *   off1[f], the INSTANCE rows of frame f are row0_f .. row0_f + K_f - 1, N = last - first after clamping.
+ * Everything below is float64 from the float32 / int32 entries, only + - * / and sqrt, every operation rounded on its own (no
+ * contraction), in exactly the grouping written.
+ *   1. Links.  For an instance row r of frame f: row_frame[r] = f, and next_row[r] = the first row r' with prev_row[r'] == r and
+ *      track[r'] == track[r] among the instance rows of the frames f+1 .. min(f + CMF_TRACK_MAX_GAP + 1, last - 1) that own rows,
+ *      frames ascending (top carried on from frame f), rows ascending inside a frame; -1 where there is none.  So a successor
+ *      lies in a strictly later frame, no row has two predecessors that count, and no chain of links is longer than N.
+ *      r is a HEAD unless p = prev_row[r] satisfies base <= p < row0_f and next_row[p] == r.  Every instance row of tables that
+ *      cmf_track_instances produced lies on the chain of exactly one head: the track's matches in frame order.
+ *   2. Measurements of row k at frame f, c = centroid[k], d = disp[k] (disp is in scan-2 axes, cmf_track_instances step 7):
+ *        zp_r = ((W[r][0] c0 + W[r][1] c1) + W[r][2] c2) + W[r][3]   (W = W_f)
+ *        zd_r = (A[r][0] d0 + A[r][1] d1) + A[r][2] d2                (A = A_f)
+ *   3. Filter, along a head's chain.  The state per axis r is (p_r, v_r), v in metres per frame; the covariance (a, b, c) =
+ *      (P_pp, P_pv, P_vv) is one for the three axes.  At the head: p = zp, v = zd, (a, b, c) = (rp, 0, rd).  At every later row
+ *      k, with g = (double)min(max(gap[k], 1), CMF_TRACK_MAX_GAP + 1):
+ *        PREDICT  pm_r = p_r + g v_r                                 (the velocity is kept)
+ *                 am = (a + g ((2 b) + g c)) + (q ((g g) g)) / 3     bm = (b + g c) + (q (g g)) / 2     cm = c + q g
+ *        UPDATE   (H = I, R = diag(rp, rd), the gain by the closed-form inverse of the innovation covariance)
+ *                 s11 = am + rp   s12 = bm   s22 = cm + rd   det = s11 s22 - s12 s12
+ *                 k11 = (am s22 - bm s12) / det   k12 = (bm s11 - am s12) / det
+ *                 k21 = (bm s22 - cm s12) / det   k22 = (cm s11 - bm s12) / det
+ *                 ep_r = zp_r - pm_r   ev_r = zd_r - v_r
+ *                 p_r = pm_r + (k11 ep_r + k12 ev_r)   v_r = v_r + (k21 ep_r + k22 ev_r)
+ *                 a = am - (k11 am + k12 bm)   b = bm - (k11 bm + k12 cm)   c = cm - (k21 bm + k22 cm)
+ *      and filt[k] = (p0 p1 p2 v0 v1 v2), fcov[k] = (a b c).
+ *   4. Smoother, backwards over the same chain from the filtered values alone.  At the chain's last row state = filt, scov = fcov.
+ *      For a row j whose successor is k (g from gap[k] as above; (p, v, a, b, c) the FILTERED values of j, (ps, vs, as, bs, cs) the
+ *      SMOOTHED values of k), the prediction is formed again by the expressions of PREDICT, then
+ *        m11 = a + g b   m12 = b   m21 = b + g c   m22 = c   dm = am cm - bm bm
+ *        c11 = (m11 cm - m12 bm) / dm   c12 = (m12 am - m11 bm) / dm   c21 = (m21 cm - m22 bm) / dm   c22 = (m22 am - m21 bm) / dm
+ *        dp_r = ps_r - pm_r   dv_r = vs_r - v_r
+ *        state[j] = (p_r + (c11 dp_r + c12 dv_r), v_r + (c21 dp_r + c22 dv_r))
+ *        da = as - am   db = bs - bm   dc = cs - cm
+ *        e11 = c11 da + c12 db   e12 = c11 db + c12 dc   e21 = c21 da + c22 db   e22 = c21 db + c22 dc
+ *        scov[j] = (a + (e11 c11 + e12 c12), b + (e11 c21 + e12 c22), c + (e21 c21 + e22 c22))
+ *   5. Back into the frame's own scan-1 axes, for every instance row with (x, v) = state[r] and W = W_f, by the rigid inverse
+ *      (R^T, -R^T t) of cmf_pose_chain, whether or not R is exactly orthonormal:
+ *        ti_r = -((W[0][r] W[0][3] + W[1][r] W[1][3]) + W[2][r] W[2][3])
+ *        P_r = ((W[0][r] x0 + W[1][r] x1) + W[2][r] x2) + ti_r        V_r = (W[0][r] v0 + W[1][r] v1) + W[2][r] v2
+ *      pos = (float)P, vel = (float)V.
+ *   6. Heading.  s2 = V_0 V_0 + V_1 V_1.  If s2 >= min_disp2 and s2 > 0 (a NaN is neither): s = sqrt(s2), heading = ((float)(V_0 / s),
+ *      (float)(V_1 / s)), heading_src = 1.  Otherwise heading = (1, 0), heading_src = 0: the axis-aligned box the instance has.
+ *   7. Box, over the frame's member points i (label[row0_f + i] == the instance's number, i = 0 .. n_f - 1 ascending) with their
+ *      float32 positions x, y, z from tab1, (hx, hy) the float32 heading AS WRITTEN taken back to float64 and c the float32 centroid:
+ *        dx = (double)x - (double)c0   dy = (double)y - (double)c1   a_i = hx dx + hy dy   b_i = (-hy) dx + hx dy
+ *      amin, amax, bmin, bmax by comparison from the first member (replaced only where a value is smaller, larger), lo_z, hi_z
+ *      likewise over the float32 z, as the instances' lo / hi.  ma = (amin + amax) / 2, mb = (bmin + bmax) / 2 and
+ *        box_size   = ((float)(amax - amin), (float)(bmax - bmin), (float)((double)hi_z - (double)lo_z))
+ *        box_center = ((float)((double)c0 + (ma hx - mb hy)), (float)((double)c1 + (ma hy + mb hx)), (float)(((double)lo_z + (double)hi_z) / 2))
+ *      An instance without a member point has box_size 0 and box_center = the centroid, copied.
+ * Outputs, all in the instances' row space: row_frame, next_row (total) int32; filt, state (total,6), fcov, scov (total,3) float64,
+ *   in the clip's axes; pos, vel, box_center, box_size (total,3), heading (total,2) float32, heading_src (total) int32, in the
+ *   frame's scan-1 axes.  The rows of an owned frame behind K hold row_frame -1, next_row -1, heading_src -1 and zeros.
+ * Guarantees, as cmf_track_instances: no atomics and no global scratch; every element of an owned frame's rows is written by one
+ *   thread (steps 1 and 5-7 and the rows behind K by the row's own thread, steps 3-4 by the thread of the chain's head); rows
+ *   outside every clip are not touched.  For tables that cmf_track_instances produced the result is fully defined and independent
+ *   of the schedule.  For any other tables -- prev_row out of range or in a cycle, gap <= 0 or huge, labels, counts, offsets or
+ *   clips that do not fit -- the result is wrong data, never an access outside a buffer and never an unbounded loop: a link is
+ *   only ever followed to a row that step 1 found by its search, which lies in a strictly later owned frame of the clip, every
+ *   walk is capped by N as well, and gap is clamped.  (An instance row whose prev_row points at a row of the clip that no frame
+ *   owns may be left on no chain; its filt, state, fcov and scov are then not written.)  total <= INT_MAX.
+ *   One workgroup per clip, barriers between the phases: links (one thread per instance row), chains (sequential per track,
+ *   parallel over the heads), boxes (one thread per instance over its frame's labels); each phase works on sixteen frames side by
+ *   side from a table of the clip's rows in LDS.  A latency kernel: it keeps nclips CUs busy and lasts as long as its longest clip.  tests/objects_ref.py restates all of this in numpy, bit for bit. */
+int cmf_track_states(int nclips, int nframes, const int *clips, const int *off1, long long total, const int *count, const int *label,
+                     const float *centroid, const float *disp, const int *track, const int *prev_row, const int *gap,
+                     const float *tab1, int ld_tab, const double *poses, double rp, double rd, double q, double min_disp2,
+                     int *row_frame, int *next_row, double *filt, double *fcov, double *state, double *scov, float *pos, float *vel,
+                     float *heading, int *heading_src, float *box_center, float *box_size, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 
