@@ -17,10 +17,10 @@ in the ego-compensated frame (constant velocity over the window, no turning).
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import WHICH, to_device as _to_device         # noqa: F401  (both are reached through this module too)
 
 MAX_WINDOW = 64                                             # CMF_ACCUM_MAX_WINDOW of include/cmflow_hip.h
-WHICH = ("pred", "gt")
 DYNAMIC = ("keep", "propagate", "drop")                     # CMF_ACCUM_KEEP, CMF_ACCUM_PROPAGATE, CMF_ACCUM_DROP
 
 
@@ -53,13 +53,10 @@ def plan(counts, clips, ids, window):
     last) ranges ``clips`` (None: one clip), -> (first (nsel) int32: the first frame of every target's clip, ages (nsel) int32:
     G = min(window, id - first + 1), cap_off (nsel+1) int64: the running sum of the sources' point counts).  A frame outside every
     clip is a clip of its own.  ValueError for a window outside 1 .. 64 or an id outside the split."""
-    if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or not 1 <= window <= MAX_WINDOW:
-        raise ValueError("accumulate: window = %r (a whole number from 1 to %d)" % (window, MAX_WINDOW))
+    _frames.whole("accumulate", "window", window, 1, MAX_WINDOW)
     counts = np.asarray(counts, dtype=np.int64)
-    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
     F = counts.size
-    if ids.size and not (0 <= ids.min() and ids.max() < F):
-        raise ValueError("accumulate: frames outside 0 .. %d" % (F - 1))
+    ids = _frames.in_split(np.asarray(ids, dtype=np.int64).reshape(-1), F, "accumulate")
     start_of = np.arange(F, dtype=np.int64)                                 # outside every clip: a clip of one frame
     for a, b in ([(0, F)] if not clips else clips):
         a, b = max(int(a), 0), min(int(b), F)
@@ -70,11 +67,6 @@ def plan(counts, clips, ids, window):
     csum = np.concatenate(([0], np.cumsum(counts)))
     cap = csum[ids + 1] - csum[ids - ages + 1]                              # the sources are consecutive frames: their rows are one range
     return first.astype(np.int32), ages.astype(np.int32), np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
-
-
-def _to_device(host, dtype, device):
-    t = torch.from_numpy(np.ascontiguousarray(host)).to(dtype)
-    return t.pin_memory().to(device, non_blocking=True) if t.numel() and device.type == "cuda" else t.to(device)
 
 
 def accumulate(split, store=None, window=8, which="pred", dynamic="keep", frames=None):
@@ -93,40 +85,23 @@ def accumulate(split, store=None, window=8, which="pred", dynamic="keep", frames
     ValueError, before any launch, for a window outside 1 .. 64, an unknown ``which`` or ``dynamic``, ``'pred'`` without a store or with
     a source frame that is not done, a store of another split, ids outside the split, or 2^31 output rows and more; RuntimeError when
     the split is not on the GPU (no CPU fallback)."""
-    if which not in WHICH:
-        raise ValueError("accumulate: which = %r is not one of %s" % (which, ", ".join(WHICH)))
+    _frames.check_which(which, "accumulate")
     if dynamic not in DYNAMIC:
         raise ValueError("accumulate: dynamic = %r is not one of %s" % (dynamic, ", ".join(DYNAMIC)))
-    if which == "pred":
-        if store is None:
-            raise ValueError("accumulate: which='pred' reads a SplitResults store; pass one, or which='gt'")
-        if len(split) != len(store) or split.tab1.shape[0] != store.flow.shape[0]:     # the two comparisons of vis.check_store
-            raise ValueError("accumulate: the split is not the one these results belong to")
+    _frames.check_store(split, store, which, "accumulate")
     F = len(split)
-    if frames is None:
-        ids = np.arange(F, dtype=np.int64)
-    elif torch.is_tensor(frames):
-        if frames.dtype != torch.int64 or frames.dim() != 1:
-            raise ValueError("accumulate: frames is a list or a 1-d int64 tensor, not %s of shape %s" % (frames.dtype, tuple(frames.shape)))
-        ids = frames.detach().cpu().numpy()                                 # the one read-back of a device selection
-    else:
-        ids = np.asarray([int(f) for f in frames], dtype=np.int64)
+    ids = _frames.selected(frames, F, "accumulate", bounds=False)           # plan() takes the window first, then the bounds
     first, ages, cap_off = plan(split.counts_host[0], split.clips, ids, window)
     if which == "pred":
-        done = store.done.cpu().numpy() != 0
         need = np.zeros(F + 1, dtype=np.int64)                              # the sources of all targets, as a difference array
         np.add.at(need, ids - ages + 1, 1)
         np.add.at(need, ids + 1, -1)
-        missing = (np.cumsum(need[:F]) > 0) & ~done
-        if missing.any():
-            raise ValueError("accumulate: %d source frames have no results (first: frame %d)" % (int(missing.sum()), int(missing.argmax())))
+        _frames.need_done(store, np.cumsum(need[:F]) > 0, "accumulate", "source")
     R = int(cap_off[-1])
     if R >= 2 ** 31:
         raise ValueError("accumulate: %d output rows, more than 2^31 - 1 (select fewer frames or a shorter window)" % R)
-    split._need_gpu("accumulate")
+    flow, mask, T, gt = _frames.bind(split, store, which, "accumulate")
     dev = split.device
-    if which == "pred" and not (store.flow.is_cuda and store.flow.device == dev):
-        raise RuntimeError("accumulate: store on %s, split on %s" % (store.flow.device, dev))
     nsel = ids.size
     f32, i32, u8 = torch.float32, torch.int32, torch.uint8
     off = _to_device(cap_off, i32, dev)
@@ -140,8 +115,6 @@ def accumulate(split, store=None, window=8, which="pred", dynamic="keep", frames
     out = AccumulatedClouds(off, count, xyz, src, age, ids_d, window, which, dynamic, cap_off, ids)
     if nsel == 0:
         return out
-    gt = which == "gt"
-    flow, mask, T = (None, None, split.trans) if gt else (store.flow, store.mask, store.pred_trans)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().cmf_accumulate(
             nsel, F, None if sel is None else _lib.dev_ptr(sel, torch.int64), _lib.dev_ptr(first_d, i32), _lib.dev_ptr(split.off1, i32),

@@ -2,8 +2,7 @@
 // brought into the current sensor frame -- static points through the chained ego-motion, moving points left as a trail, dropped, or
 // carried forward by their own flow.  A DEFINITION, stated in include/cmflow_hip.h and restated in numpy, bit for bit, by
 // tests/accumulate_ref.py: float64 from the float32 inputs, a fixed operation order, no contraction anywhere in this file.
-#include "cmf_common.h"
-#include "../../include/cmflow_hip.h"
+#include "frame_tables.h"
 
 #pragma clang fp contract(off)
 
@@ -23,14 +22,11 @@ struct AccArgs {
     unsigned char *age;
 };
 
-// ((m0 x + m1 y) + m2 z) + m3, every operation rounded on its own
-__device__ __forceinline__ double acc_affine(const double *m, double x, double y, double z) { return ((m[0] * x + m[1] * y) + m[2] * z) + m[3]; }
-
 // One workgroup per target.  The transforms of the window pass through LDS (one coalesced read), lane 0 forms the chain M_0 .. M_G-1
 // from them in order (a parallel scan would change the association), and the ages are then walked oldest first with a running row
 // offset: thread t takes point c * 256 + t of the source frame and writes output row base + (its rank among the kept points), so a
 // target's rows keep age order and, inside an age, the frame's own point order.  Nothing but `drop` leaves a point out, and only `drop`
-// needs the ranks: a ballot per wave and the four waves' counts, as cmf_prepare_count.  Rows from the count to the capacity are
+// needs the ranks (ft_block_rank of frame_tables.h).  Rows from the count to the capacity are
 // written as padding by the same workgroup, so every row of the capacity is written exactly once.
 template <bool DROP>
 __global__ __launch_bounds__(ACC_THREADS) void accumulate_kernel(const AccArgs a)
@@ -40,9 +36,7 @@ __global__ __launch_bounds__(ACC_THREADS) void accumulate_kernel(const AccArgs a
     __shared__ int s_cnt[ACC_WAVES];
     const int tid = threadIdx.x, lane = tid & (CMF_WAVE - 1), wave = tid / CMF_WAVE;
     const int s = blockIdx.x;
-    long long fj = a.frames ? a.frames[s] : (long long)s;
-    fj = fj < 0 ? 0 : fj > a.F - 1 ? a.F - 1 : fj;
-    const int j = (int)fj;
+    const int j = ft_selected_frame(a.frames, s, a.F);
     const int first = min(max(a.first[s], 0), j);
     const int G = min(a.window, j - first + 1);                            // 1 <= G <= CMF_ACCUM_MAX_WINDOW: sources j-G+1 .. j, all >= first >= 0
     const long long cap0 = a.cap_off[s];
@@ -76,9 +70,8 @@ __global__ __launch_bounds__(ACC_THREADS) void accumulate_kernel(const AccArgs a
     long long base = 0;                                                    // rows of this target written so far
     for (int g = G - 1; g >= 0; --g) {
         const int i = j - g;
-        const long long start = a.off1[i];
-        long long n = (long long)a.off1[i + 1] - start;
-        if (start < 0 || n < 0 || start + n > a.total) n = 0;              // a frame outside the tables is empty
+        long long start, n;
+        ft_frame_rows(a.off1, i, a.total, start, n);                       // a frame outside the tables is empty
         const double *M = s_M[g], *N = s_M[g > 0 ? g - 1 : 0];
         const float *Ti = s_T[g];
         for (long long p0 = 0; p0 < n; p0 += ACC_THREADS) {
@@ -92,17 +85,9 @@ __global__ __launch_bounds__(ACC_THREADS) void accumulate_kernel(const AccArgs a
             }
             long long dst = base + (p - p0);
             if (DROP) {
-                const unsigned long long hits = __ballot(keep);
-                const int lower = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hits, 0u));
-                if (lane == 0) s_cnt[wave] = __popcll(hits);
-                __syncthreads();
-                int before = 0, all = 0;
-                for (int w = 0; w < ACC_WAVES; ++w) {
-                    before += w < wave ? s_cnt[w] : 0;
-                    all += s_cnt[w];
-                }
-                __syncthreads();                                           // the next chunk overwrites s_cnt
-                dst = base + before + lower;
+                int before, all;
+                ft_block_rank<ACC_WAVES>(keep, lane, wave, s_cnt, before, all);
+                dst = base + before;
                 base += all;
             } else {
                 base += min((long long)ACC_THREADS, n - p0);
@@ -114,18 +99,16 @@ __global__ __launch_bounds__(ACC_THREADS) void accumulate_kernel(const AccArgs a
                     o[0] = q[0]; o[1] = q[1]; o[2] = q[2];                 // the current scan: copied bit for bit
                 } else {
                     const double px = (double)q[0], py = (double)q[1], pz = (double)q[2];
-                    double x = acc_affine(M, px, py, pz), y = acc_affine(M + 4, px, py, pz), z = acc_affine(M + 8, px, py, pz);
+                    double x = ft_affine(M, px, py, pz), y = ft_affine(M + 4, px, py, pz), z = ft_affine(M + 8, px, py, pz);
                     if (a.mode == CMF_ACCUM_PROPAGATE && moving) {
                         const float *f = a.gt ? q + 6 : a.flow + 3 * row;
-                        double t[12];
+                        double t[12], d[3];
                         for (int e = 0; e < 12; ++e) t[e] = (double)Ti[e];
-                        const double d0 = (px + (double)f[0]) - acc_affine(t, px, py, pz);
-                        const double d1 = (py + (double)f[1]) - acc_affine(t + 4, px, py, pz);
-                        const double d2 = (pz + (double)f[2]) - acc_affine(t + 8, px, py, pz);
+                        ft_own_motion(t, px, py, pz, f, d);
                         const double k = (double)g;
-                        x = x + k * ((N[0] * d0 + N[1] * d1) + N[2] * d2);
-                        y = y + k * ((N[4] * d0 + N[5] * d1) + N[6] * d2);
-                        z = z + k * ((N[8] * d0 + N[9] * d1) + N[10] * d2);
+                        x = x + k * ((N[0] * d[0] + N[1] * d[1]) + N[2] * d[2]);
+                        y = y + k * ((N[4] * d[0] + N[5] * d[1]) + N[6] * d[2]);
+                        z = z + k * ((N[8] * d[0] + N[9] * d[1]) + N[10] * d[2]);
                     }
                     o[0] = (float)x; o[1] = (float)y; o[2] = (float)z;
                 }

@@ -2,8 +2,7 @@
 // frame's moving points by position and by the displacement they show against the ego-motion.  A DEFINITION, stated in
 // include/cmflow_hip.h and restated in numpy, bit for bit, by tests/instances_ref.py: float64 from the float32 inputs, a fixed
 // operation order, no contraction anywhere in this file, and no dependence on the order in which threads run.
-#include "cmf_common.h"
-#include "../../include/cmflow_hip.h"
+#include "frame_tables.h"
 
 #pragma clang fp contract(off)
 
@@ -25,28 +24,8 @@ struct InstArgs {
     float *centroid, *disp, *lo, *hi;
 };
 
-// ((m0 x + m1 y) + m2 z) + m3, every operation rounded on its own: cmf_accumulate's tp
-__device__ __forceinline__ double inst_affine(const double *m, double x, double y, double z) { return ((m[0] * x + m[1] * y) + m[2] * z) + m[3]; }
-
-// ranks of the set flags of one chunk of INST_THREADS threads, in thread order: -> (flags of lower threads, flags of the chunk).
-// Two barriers.
-__device__ __forceinline__ void inst_chunk_rank(bool flag, int lane, int wave, int *s_cnt, int &before, int &all)
-{
-    const unsigned long long hits = __ballot(flag);
-    const int lower = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hits, 0u));
-    if (lane == 0) s_cnt[wave] = __popcll(hits);
-    __syncthreads();
-    before = lower;
-    all = 0;
-    for (int w = 0; w < INST_WAVES; ++w) {
-        before += w < wave ? s_cnt[w] : 0;
-        all += s_cnt[w];
-    }
-    __syncthreads();                                                       // the next chunk overwrites s_cnt
-}
-
-// One workgroup of 1024 threads per selected frame.  The candidates are compacted into LDS in point order (a ballot per wave and the
-// waves' counts, as cmf_accumulate's `drop`), so a candidate's slot c orders like its point index and "lowest index" can be decided
+// One workgroup of 1024 threads per selected frame.  The candidates are compacted into LDS in point order (ft_block_rank of
+// frame_tables.h over each chunk of 1024 points), so a candidate's slot c orders like its point index and "lowest index" can be decided
 // on slots.  Thread t owns slot t: it alone writes what belongs to it, in LDS and in global memory, and wave w owns the slots
 // 64 w .. 64 w + 63 -- a ballot of the wave is word w of a bit set over the slots.
 // Every pair distance is formed ONCE: the thread walks all slots j (the same j for every lane: LDS broadcasts) and keeps its row of the
@@ -67,12 +46,9 @@ __global__ __launch_bounds__(INST_THREADS) void cluster_moving_kernel(const Inst
     __shared__ int s_cnt[INST_WAVES];
     const int tid = threadIdx.x, lane = tid & (CMF_WAVE - 1), wave = tid / CMF_WAVE;
     const int s = blockIdx.x;
-    long long ff = a.frames ? a.frames[s] : (long long)s;
-    ff = ff < 0 ? 0 : ff > a.F - 1 ? a.F - 1 : ff;
-    const int f = (int)ff;
-    const long long start = a.off1[f];
-    long long n_ll = (long long)a.off1[f + 1] - start;
-    if (start < 0 || n_ll < 0 || start + n_ll > a.total) n_ll = 0;         // a frame outside the tables owns no rows
+    const int f = ft_selected_frame(a.frames, s, a.F);
+    long long start, n_ll;
+    ft_frame_rows(a.off1, f, a.total, start, n_ll);                        // a frame outside the tables owns no rows
     const int n = (int)n_ll;                                               // total <= INT_MAX
     const size_t row0 = (size_t)start;
     const bool too_large = n > CMF_INST_MAX_POINTS;                        // treated as empty: nothing is a candidate
@@ -93,7 +69,7 @@ __global__ __launch_bounds__(INST_THREADS) void cluster_moving_kernel(const Inst
             }
         }
         int before, all;
-        inst_chunk_rank(cand, lane, wave, s_cnt, before, all);
+        ft_block_rank<INST_WAVES>(cand, lane, wave, s_cnt, before, all);
         if (cand) {                                                        // only where n <= 1024: m + before < n
             const int c = m + before;
             const size_t row = row0 + p;
@@ -101,9 +77,7 @@ __global__ __launch_bounds__(INST_THREADS) void cluster_moving_kernel(const Inst
             const float *fl = a.gt ? q + 6 : a.flow + 3 * row;
             const double px = (double)q[0], py = (double)q[1], pz = (double)q[2];
             s_p[c][0] = q[0]; s_p[c][1] = q[1]; s_p[c][2] = q[2];
-            s_d[c][0] = (px + (double)fl[0]) - inst_affine(T, px, py, pz);
-            s_d[c][1] = (py + (double)fl[1]) - inst_affine(T + 4, px, py, pz);
-            s_d[c][2] = (pz + (double)fl[2]) - inst_affine(T + 8, px, py, pz);
+            ft_own_motion(T, px, py, pz, fl, s_d[c]);
             s_idx[c] = p;
         }
         m += all;
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(INST_THREADS) void cluster_moving_kernel(const Inst
     {
         const bool root = core && lab[tid] == tid;
         int before;
-        inst_chunk_rank(root, lane, wave, s_cnt, before, K);
+        ft_block_rank<INST_WAVES>(root, lane, wave, s_cnt, before, K);
         if (root) {
             rank[tid] = before;
             s_seed[before] = tid;

@@ -4,8 +4,7 @@
 // oriented along it.  A DEFINITION, stated in include/cmflow_hip.h and restated in numpy, bit for bit, by tests/objects_ref.py:
 // float64 from the float32 inputs, + - * / and sqrt only, a fixed operation order, no contraction anywhere in this file, and no
 // dependence on the order in which threads run.
-#include "cmf_common.h"
-#include "../../include/cmflow_hip.h"
+#include "frame_tables.h"
 
 #pragma clang fp contract(off)
 
@@ -36,8 +35,8 @@ struct FrameTable {
     long long top;                                                         // top behind the chunk's last frame
 };
 
-// The rows of the frames f0 .. f0 + OBJ_TABLE - 1 of a clip (cut at its end), as cmf_track_instances walks them: frame f owns its rows
-// iff top <= off1[f] <= off1[f+1] <= total.  The loads are spread over the workgroup, the walk itself (top is sequential) is thread
+// The rows of the frames f0 .. f0 + OBJ_TABLE - 1 of a clip (cut at its end), walked by ft_clip_frame of frame_tables.h as the tracker
+// walks them.  The loads are spread over the workgroup, the walk itself (top is sequential) is thread
 // 0's over LDS.  -> top behind the chunk proper.  Called by every thread; three barriers.
 __device__ __forceinline__ long long obj_chunk(const StateArgs &a, bool clip_ok, int f0, int end, long long top, FrameTable &t)
 {
@@ -51,14 +50,11 @@ __device__ __forceinline__ long long obj_chunk(const StateArgs &a, bool clip_ok,
         long long at = top, behind = top;
         for (int i = 0; i < m; ++i) {
             const long long start = t.off[i], stop = t.off[i + 1];
-            const bool owns = clip_ok && start >= at && stop >= start && stop <= a.total;
-            const int n = owns ? (int)(stop - start) : 0;
-            if (owns) at = stop;
-            int K = owns ? t.cnt[i] : 0;
-            K = K < 0 ? 0 : K > n ? n : K;
+            int n;
+            const bool owns = ft_clip_frame(clip_ok, start, stop, a.total, at, n);
             t.start[i] = owns ? (int)start : 0;
             t.n[i] = n;
-            t.K[i] = K > CMF_TRACK_MAX_LIVE ? CMF_TRACK_MAX_LIVE : K;
+            t.K[i] = ft_clip_frame_instances(owns, t.cnt + i, n);
             if (i < OBJ_CHUNK) behind = at;
         }
         t.top = behind;
@@ -106,12 +102,11 @@ __global__ __launch_bounds__(OBJ_THREADS) void track_states_kernel(const StateAr
     __shared__ FrameTable tab;
     const int tid = threadIdx.x, group = tid / OBJ_LANES, lane = tid % OBJ_LANES;
     const int clip = blockIdx.x;
-    int first = a.clips[2 * clip], end = a.clips[2 * clip + 1];
-    first = first < 0 ? 0 : first > a.F ? a.F : first;
-    end = end < first ? first : end > a.F ? a.F : end;
+    int first, end;
+    long long base;
+    bool clip_ok;
+    ft_clip(a.clips, a.off1, clip, a.F, a.total, first, end, base, clip_ok);
     const int N = end - first;
-    const long long base = a.off1[first];
-    const bool clip_ok = base >= 0 && base <= a.total;
 
     // ---- (1) links and fills
     long long top = base;

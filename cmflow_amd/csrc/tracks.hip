@@ -3,8 +3,7 @@
 // matching against a constant-displacement prediction.  A DEFINITION, stated in include/cmflow_hip.h and restated in numpy, bit for
 // bit, by tests/tracks_ref.py: float64 from the float32 inputs, a fixed operation order, no contraction anywhere in this file, and
 // no dependence on the order in which threads run.
-#include "cmf_common.h"
-#include "../../include/cmflow_hip.h"
+#include "frame_tables.h"
 
 #pragma clang fp contract(off)
 
@@ -21,23 +20,6 @@ struct TrackArgs {
     int *track, *prev_row, *gap, *age, *point_track, *birth, *last, *hits, *ntracks, *overflow;
     float *pred;
 };
-
-// ranks of the set flags of the workgroup, in thread order: -> (flags of lower threads, flags of the workgroup).  Two barriers: the
-// ballot scan of cmf_cluster_moving.
-__device__ __forceinline__ void trk_rank(bool flag, int lane, int wave, int *s_cnt, int &before, int &all)
-{
-    const unsigned long long hits = __ballot(flag);
-    const int lower = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hits, 0u));
-    if (lane == 0) s_cnt[wave] = __popcll(hits);
-    __syncthreads();
-    before = lower;
-    all = 0;
-    for (int w = 0; w < TRK_WAVES; ++w) {
-        before += w < wave ? s_cnt[w] : 0;
-        all += s_cnt[w];
-    }
-    __syncthreads();                                                       // the next scan overwrites s_cnt
-}
 
 // G2 of the header: e_r = P_r - c_r, (e0 e0 + e1 e1) + e2 e2 -- ONE expression for both sides of an edge, so a cost formed again
 // (by the track, by the instance, in a later round) is formed from the same operands in the same order
@@ -77,6 +59,8 @@ __global__ __launch_bounds__(TRK_THREADS) void track_instances_kernel(const Trac
     __shared__ int s_cnt[TRK_WAVES];
     const int tid = threadIdx.x, lane = tid & (CMF_WAVE - 1), wave = tid / CMF_WAVE;
     const int clip = blockIdx.x;
+    // ft_clip and, per frame, ft_clip_frame / ft_clip_frame_instances of frame_tables.h, written out: this kernel's inner loops are
+    // scheduled differently around the inlined helpers and the launch takes 1 % longer
     int first = a.clips[2 * clip], end = a.clips[2 * clip + 1];
     first = first < 0 ? 0 : first > a.F ? a.F : first;
     end = end < first ? first : end > a.F ? a.F : end;
@@ -204,7 +188,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_instances_kernel(const Trac
         // ---- unmatched instances open tracks, in ascending j: the instance's owner writes its row
         const bool born = isI && mu < 0;
         int r_born, births, r_coast, coasts;
-        trk_rank(born, lane, wave, s_cnt, r_born, births);
+        ft_block_rank<TRK_WAVES>(born, lane, wave, s_cnt, r_born, births);
         if (born) {
             const size_t row = row0 + tid;
             a.track[row] = next_id + r_born;
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_instances_kernel(const Trac
             s_born[r_born] = tid;
         }
         // ---- capacity: matched tracks and births are K <= 1024 and always fit; the coasting tracks go first
-        trk_rank(coasting, lane, wave, s_cnt, r_coast, coasts);
+        ft_block_rank<TRK_WAVES>(coasting, lane, wave, s_cnt, r_coast, coasts);
         if (K + coasts > CMF_TRACK_MAX_LIVE) {
             overflow += 1;
             dying = dying || coasting;
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_instances_kernel(const Trac
         // ---- the births take the lowest free slots (the scan's barriers are also what makes s_born and s_itrack visible)
         {
             int r_free, frees;
-            trk_rank(!live, lane, wave, s_cnt, r_free, frees);
+            ft_block_rank<TRK_WAVES>(!live, lane, wave, s_cnt, r_free, frees);
             if (!live && r_free < births) {                                // survivors + births <= 1024: frees >= births
                 const int j = s_born[r_free];
                 const size_t row = row0 + j;

@@ -5,8 +5,7 @@
 //   cmf_vis_render_bev:   hard discs in index order (the last drawn point over a pixel wins) plus the range / bearing guides, as a
 //                         DEFINITION in float32 that uses + - * and compares only.
 // Both are restated in numpy, bit for bit (tests/vis_ref.py): no contraction anywhere in this file.
-#include "cmf_common.h"
-#include "../../include/cmflow_hip.h"
+#include "frame_tables.h"
 
 #pragma clang fp contract(off)
 
@@ -40,15 +39,13 @@ struct ColorArgs {
     unsigned char *colors, *drawn;
 };
 
-// The frame of selection slot `s` and its rows [start, start + n) of the store; a bad id is clamped, offsets that do not describe the
-// store give n = 0.
+// The frame of selection slot `s` and its rows [start, start + n) of the store (frame_tables.h: a bad id is clamped, offsets that do not
+// describe the store give n = 0).
 __device__ __forceinline__ void vis_frame_rows(const long long *frames, const int *off1, int F, long long total, int s, long long &start, int &n)
 {
-    long long f = frames ? frames[s] : (long long)s;
-    f = f < 0 ? 0 : f > F - 1 ? F - 1 : f;
-    start = off1[f];
-    n = off1[f + 1] - off1[f];
-    if (start < 0 || n < 0 || start + n > total) n = 0;
+    long long rows;
+    ft_frame_rows(off1, ft_selected_frame(frames, s, F), total, start, rows);
+    n = (int)rows;                                                         // off1 is int32: rows <= INT_MAX
 }
 
 // floor(255 col) as a byte: col lies in [0, 1] for every finite input; anything else (a NaN flow) becomes 0.

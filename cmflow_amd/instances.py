@@ -15,13 +15,11 @@ instance has a centroid, an axis-aligned extent and a mean displacement), no gro
 rule, and ``agreement`` compares two clusterings), and nothing is claimed about real data beyond the reference's twelve saved
 frames the tests go through.
 """
-import math
-
 import numpy as np
 import torch
 
-from . import _lib
-from .accumulate import WHICH, _to_device
+from . import _frames, _lib
+from ._frames import WHICH                                  # noqa: F401  (``instances.WHICH``)
 
 MAX_POINTS = 1024                                           # CMF_INST_MAX_POINTS of include/cmflow_hip.h
 NONE, NOISE, BORDER, CORE = 0, 1, 2, 3                      # CMF_INST_NONE .. CMF_INST_CORE: the values of ``kind``
@@ -74,19 +72,7 @@ class FrameInstances:
     def velocity(self):
         """(sum n1, 3) float32, in the instance tables' row space: ``disp`` over the frame's ``split.interval`` -- the instance's mean
         velocity against the ground in the sensor's scan-1 axes, metres per second.  Rows that hold no instance are 0."""
-        total = self.disp.shape[0]
-        per_row = torch.repeat_interleave(self.interval, (self.off[1:] - self.off[:-1]).long(), output_size=total)
-        return self.disp / per_row[:, None]
-
-
-def _selected(frames, F, what):
-    if frames is None:
-        return np.arange(F, dtype=np.int64)
-    if torch.is_tensor(frames):
-        if frames.dtype != torch.int64 or frames.dim() != 1:
-            raise ValueError("%s: frames is a list or a 1-d int64 tensor, not %s of shape %s" % (what, frames.dtype, tuple(frames.shape)))
-        return frames.detach().cpu().numpy()                                # the one read-back of a device selection
-    return np.asarray([int(f) for f in frames], dtype=np.int64)
+        return self.disp / _frames.per_row(self.interval, self.off, self.disp.shape[0])[:, None]
 
 
 def cluster(split, store=None, which="pred", eps=2.0, min_points=2, flow_weight=0.0, frames=None):
@@ -104,40 +90,25 @@ def cluster(split, store=None, which="pred", eps=2.0, min_points=2, flow_weight=
     ValueError, before any launch, for an unknown ``which``, ``'pred'`` without a store or with a store of another split, ``eps``
     not finite or <= 0, ``flow_weight`` negative or not finite, ``min_points < 1``, ids outside the split, a selected frame of more
     than 1024 points, or a selected frame that is not done; RuntimeError when the split is not on the GPU (no CPU fallback)."""
-    if which not in WHICH:
-        raise ValueError("cluster: which = %r is not one of %s" % (which, ", ".join(WHICH)))
-    if which == "pred":
-        if store is None:
-            raise ValueError("cluster: which='pred' reads a SplitResults store; pass one, or which='gt'")
-        if len(split) != len(store) or split.tab1.shape[0] != store.flow.shape[0]:     # the two comparisons of vis.check_store
-            raise ValueError("cluster: the split is not the one these results belong to")
-    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not math.isfinite(eps) or not eps > 0:
-        raise ValueError("cluster: eps = %r (a finite number above 0, metres)" % (eps,))
-    if isinstance(flow_weight, bool) or not isinstance(flow_weight, (int, float, np.integer, np.floating)) or not math.isfinite(flow_weight) \
-            or flow_weight < 0:
-        raise ValueError("cluster: flow_weight = %r (a finite number, 0 or above)" % (flow_weight,))
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= min_points < 2 ** 31:
-        raise ValueError("cluster: min_points = %r (a whole number, 1 or above)" % (min_points,))
+    _frames.check_which(which, "cluster")
+    _frames.check_store(split, store, which, "cluster")
+    _frames.number("cluster", "eps", eps, False, "a finite number above 0, metres")
+    _frames.number("cluster", "flow_weight", flow_weight, True, "a finite number, 0 or above")
+    _frames.whole("cluster", "min_points", min_points, 1)
     F = len(split)
-    ids = _selected(frames, F, "cluster")
-    if ids.size and not (0 <= ids.min() and ids.max() < F):
-        raise ValueError("cluster: frames outside 0 .. %d" % (F - 1))
+    ids = _frames.selected(frames, F, "cluster")
     counts = np.asarray(split.counts_host[0], dtype=np.int64)
     large = counts[ids] > MAX_POINTS
     if large.any():
         raise ValueError("cluster: frame %d has %d points, more than the %d one workgroup clusters in its LDS"
                          % (int(ids[large.argmax()]), int(counts[ids[large.argmax()]]), MAX_POINTS))
     if which == "pred":
-        missing = store.done.cpu().numpy()[ids] == 0
-        if missing.any():
-            raise ValueError("cluster: %d selected frames have no results (first: frame %d)" % (int(missing.sum()), int(ids[missing.argmax()])))
-    split._need_gpu("cluster")
+        _frames.need_done(store, ids, "cluster", "selected")
+    flow, mask, T, gt = _frames.bind(split, store, which, "cluster")
     dev = split.device
-    if which == "pred" and not (store.flow.is_cuda and store.flow.device == dev):
-        raise RuntimeError("cluster: store on %s, split on %s" % (store.flow.device, dev))
     total, nsel = split.tab1.shape[0], ids.size
     f32, i32, u8 = torch.float32, torch.int32, torch.uint8
-    sel = None if frames is None else _to_device(ids, torch.int64, dev)
+    sel = None if frames is None else _frames.to_device(ids, torch.int64, dev)
     ids_d = torch.arange(F, dtype=torch.int64, device=dev) if frames is None else sel
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
     label, kind, count = torch.full((total,), -1, dtype=i32, device=dev), z((total,), u8), z((F,), i32)
@@ -146,8 +117,6 @@ def cluster(split, store=None, which="pred", eps=2.0, min_points=2, flow_weight=
     out = FrameInstances(split.off1, ids_d, label, kind, count, tables, split.interval, which, eps, min_points, flow_weight, off_host, ids)
     if nsel == 0:
         return out
-    gt = which == "gt"
-    flow, mask, T = (None, None, split.trans) if gt else (store.flow, store.mask, store.pred_trans)
     eps2, w2 = float(eps) * float(eps), float(flow_weight) * float(flow_weight)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().cmf_cluster_moving(

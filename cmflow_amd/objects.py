@@ -20,13 +20,10 @@ tracks are not formed again with the smoothed prediction; a radar sees part of a
 extent of the points seen, not the object's (``track_size`` takes the largest over a track); and nothing is claimed about real data
 beyond the reference's twelve saved frames the tests go through.
 """
-import math
-
 import numpy as np
 import torch
 
-from . import _lib
-from .accumulate import _to_device
+from . import _frames, _lib
 from .tracks import InstanceTracks
 
 PER_INSTANCE = ("row_frame", "next_row", "filt", "fcov", "state", "scov", "pos", "vel", "heading", "heading_src", "box_center", "box_size")
@@ -72,9 +69,7 @@ class TrackObjects:
     def velocity(self):
         """(sum n1, 3) float32: ``vel`` over the frame's ``split.interval`` -- the smoothed velocity against the ground in the frame's
         scan-1 axes, metres per second (as ``FrameInstances.velocity``).  Rows that hold no instance are 0."""
-        total = self.vel.shape[0]
-        per_row = torch.repeat_interleave(self.interval, (self.off[1:] - self.off[:-1]).long(), output_size=total)
-        return self.vel / per_row[:, None]
+        return self.vel / _frames.per_row(self.interval, self.off, self.vel.shape[0])[:, None]
 
     def yaw(self):
         """(sum n1) float32: the heading as an angle, ``atan2(heading_y, heading_x)`` in torch -- a convenience, not part of the
@@ -95,9 +90,7 @@ class TrackObjects:
 
 
 def _sigma(name, v, zero_ok):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
-        raise ValueError("estimate: %s = %r (a finite number %s)" % (name, v, "0 or above" if zero_ok else "above 0"))
-    return float(v)
+    return _frames.number("estimate", name, v, zero_ok, "a finite number %s" % ("0 or above" if zero_ok else "above 0"))
 
 
 def estimate(trk, split, store=None, sigma_pos=0.5, sigma_disp=0.25, sigma_acc=0.25, min_disp=0.05):
@@ -118,21 +111,13 @@ def estimate(trk, split, store=None, sigma_pos=0.5, sigma_disp=0.25, sigma_acc=0
     if not isinstance(trk, InstanceTracks):
         raise ValueError("estimate: trk is a track() result, not %s" % type(trk).__name__)
     inst = trk.inst
-    if trk.which == "pred" and store is None:
-        raise ValueError("estimate: these tracks were formed with which='pred'; pass the SplitResults store their transforms are in")
+    _frames.check_upstream(split, store, trk, trk.track, "estimate", "tracks", "formed")
     F = len(split)
-    if F != trk.off.numel() - 1 or split.tab1.shape[0] != trk.track.shape[0]:
-        raise ValueError("estimate: the split is not the one these tracks belong to")
-    if trk.which == "pred" and (F != len(store) or split.tab1.shape[0] != store.flow.shape[0]):
-        raise ValueError("estimate: the split is not the one these results belong to")
     sigma_pos, sigma_disp = _sigma("sigma_pos", sigma_pos, False), _sigma("sigma_disp", sigma_disp, False)
     sigma_acc, min_disp = _sigma("sigma_acc", sigma_acc, True), _sigma("min_disp", min_disp, True)
-    split._need_gpu("estimate")
+    T = _frames.transforms(split, store, trk.which)
+    _frames.on_device(split, (("tracks", trk.track), ("instances", inst.label), ("transforms", T)), "estimate", "object states")
     dev = split.device
-    T = store.pred_trans if trk.which == "pred" else split.trans
-    for what, t in (("tracks", trk.track), ("instances", inst.label), ("transforms", T)):
-        if not (t.is_cuda and t.device == dev):
-            raise RuntimeError("estimate: %s on %s, split on %s (object states are formed on the GPU only, no CPU fallback)" % (what, t.device, dev))
     total, C = split.tab1.shape[0], trk.clips_host.shape[0]
     i32, f32, f64 = torch.int32, torch.float32, torch.float64
     full = lambda shape, v, dt: torch.full(shape, v, dtype=dt, device=dev)
@@ -143,7 +128,7 @@ def estimate(trk, split, store=None, sigma_pos=0.5, sigma_disp=0.25, sigma_acc=0
     base = np.zeros(F, dtype=np.int64)                                      # per frame, the first row of its clip: host arithmetic
     for a, b in trk.clips_host:
         base[int(a):int(b)] = int(trk.offsets_host[int(a)])
-    out = TrackObjects(trk, arrays, poses, _to_device(base, torch.int64, dev), split.interval, sigma_pos, sigma_disp, sigma_acc, min_disp)
+    out = TrackObjects(trk, arrays, poses, _frames.to_device(base, torch.int64, dev), split.interval, sigma_pos, sigma_disp, sigma_acc, min_disp)
     if C == 0:
         return out
     p = _lib.dev_ptr

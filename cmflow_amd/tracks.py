@@ -15,13 +15,10 @@ comes back), merge or split handling (two objects clustered as one instance are 
 identities (the split has none: ``which='gt'`` tracks the instances of the labelled moving points by the same rule), and nothing
 is claimed about real data beyond the reference's twelve saved frames the tests go through.
 """
-import math
-
 import numpy as np
 import torch
 
-from . import _lib
-from .accumulate import _to_device
+from . import _frames, _lib
 from .instances import FrameInstances
 
 MAX_LIVE = 1024                                             # CMF_TRACK_MAX_LIVE of include/cmflow_hip.h
@@ -114,31 +111,21 @@ def track(inst, split, store=None, gate=2.0, max_gap=2):
     overlap; RuntimeError when the split or the instances are not on the GPU or lie on different devices (no CPU fallback)."""
     if not isinstance(inst, FrameInstances):
         raise ValueError("track: inst is a cluster() result, not %s" % type(inst).__name__)
-    if inst.which == "pred" and store is None:
-        raise ValueError("track: these instances were clustered with which='pred'; pass the SplitResults store their transforms are in")
+    _frames.check_upstream(split, store, inst, inst.label, "track", "instances", "clustered")
+    _frames.number("track", "gate", gate, False, "a finite number above 0, metres")
+    _frames.whole("track", "max_gap", max_gap, 0, MAX_GAP)
     F = len(split)
-    if F != inst.off.numel() - 1 or split.tab1.shape[0] != inst.label.shape[0]:
-        raise ValueError("track: the split is not the one these instances belong to")
-    if inst.which == "pred" and (F != len(store) or split.tab1.shape[0] != store.flow.shape[0]):
-        raise ValueError("track: the split is not the one these results belong to")
-    if isinstance(gate, bool) or not isinstance(gate, (int, float, np.integer, np.floating)) or not math.isfinite(gate) or not gate > 0:
-        raise ValueError("track: gate = %r (a finite number above 0, metres)" % (gate,))
-    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, np.integer)) or not 0 <= max_gap <= MAX_GAP:
-        raise ValueError("track: max_gap = %r (a whole number from 0 to %d)" % (max_gap, MAX_GAP))
     clips_host = plan_clips(F, split.clips)
-    split._need_gpu("track")
+    T = _frames.transforms(split, store, inst.which)
+    _frames.on_device(split, (("instances", inst.label), ("transforms", T)), "track", "tracks")
     dev = split.device
-    T = store.pred_trans if inst.which == "pred" else split.trans
-    for what, t in (("instances", inst.label), ("transforms", T)):
-        if not (t.is_cuda and t.device == dev):
-            raise RuntimeError("track: %s on %s, split on %s (tracks are formed on the GPU only, no CPU fallback)" % (what, t.device, dev))
     total, C = split.tab1.shape[0], clips_host.shape[0]
     i32, f32 = torch.int32, torch.float32
     full = lambda shape, v, dt=i32: torch.full(shape, v, dtype=dt, device=dev)
     arrays = (full((total,), -1), full((total,), -1), full((total,), 0), full((total,), 0), full((total, 3), 0.0, f32), full((total,), -1),
               full((total,), -1), full((total,), -1), full((total,), 0))
     ntracks, overflow = full((C,), 0), full((C,), 0)
-    clips = _to_device(clips_host, i32, dev)
+    clips = _frames.to_device(clips_host, i32, dev)
     out = InstanceTracks(inst, arrays, ntracks, overflow, clips, clips_host, gate, max_gap)
     if C == 0:
         return out

@@ -19,7 +19,7 @@ import zlib
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 LAYERS = ("flow", "flow_gt", "seg", "seg_gt")               # CMF_VIS_FLOW .. CMF_VIS_SEG_GT of include/cmflow_hip.h
 MAX_SIDE = 4096                                             # CMF_VIS_MAX_SIDE
@@ -64,8 +64,7 @@ def _layer_id(layer, what):
 def check_store(store, split, what):
     """ValueError unless ``store`` is a store of ``split`` (the two comparisons of ``SplitResults.write_json``); RuntimeError unless
     both are on one GPU."""
-    if len(split) != len(store) or split.tab1.shape[0] != store.flow.shape[0]:
-        raise ValueError("%s: the split is not the one these results belong to" % what)
+    _frames.belongs(split, store, what)
     if not (store.flow.is_cuda and split.tab1.is_cuda and store.flow.device == split.tab1.device):
         raise RuntimeError("%s: store on %s, split on %s; pictures are rendered on the GPU only (no CPU fallback)"
                            % (what, store.flow.device, split.tab1.device))
@@ -78,10 +77,9 @@ def _selection(store, frames, what):
         return None, len(store)
     if not torch.is_tensor(frames):
         frames = torch.tensor([int(f) for f in frames], dtype=torch.int64)
-    if frames.dtype != torch.int64 or frames.dim() != 1:
-        raise ValueError("%s: frames is a list or a 1-d int64 tensor, not %s of shape %s" % (what, frames.dtype, tuple(frames.shape)))
+    _frames.check_frames_tensor(frames, what)
     if not frames.is_cuda:
-        frames = frames.pin_memory().to(store.device, non_blocking=True) if frames.numel() else frames.to(store.device)
+        frames = _frames.pinned(frames, store.device)
     elif frames.device != store.device:
         raise RuntimeError("%s: frames on %s, the store on %s" % (what, frames.device, store.device))
     return frames.contiguous(), int(frames.numel())

@@ -22,17 +22,12 @@ measurement is a child process under a time limit.
 
     python tools/accumulate_probe.py [--frames 256] [--rounds 9] [--reps 50] [--limit 400] [--out profiles/accumulate_probe.txt]
 """
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from tools.results_probe import EvalArgs, clips_of             # noqa: E402  (the same split as the results probe)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import _run_probe as P                               # noqa: E402
 
 WINDOWS = (8, 32)
 PEAK = 8.0e12                                                   # bytes/s
@@ -59,34 +54,16 @@ def torch_accumulate(sp, store, window, dynamic, idx):
     return q[~moving] if dynamic == "drop" else q
 
 
-def child(a):
+def measure(a):
     import numpy as np
     import torch
-    from cmflow_amd import _lib, accumulate as A, dataset as D, evaluate as EV, synth
-    from cmflow_amd.cmflow import CMFlow
-    if not torch.cuda.is_available():
-        raise SystemExit("accumulate_probe: needs the GPU")
-    dev = torch.device("cuda:0")
-    gold = os.path.join(REPO, "tests", "golden")
-    net = CMFlow(EvalArgs())
-    net.load_state_dict(synth.synth_state_dict(json.load(open(os.path.join(gold, "state_manifest_cmflow.json"))), seed=1234,
-                                               calib=os.path.join(gold, "bn_calib_cmflow.npz")))
-    sp = D.DeviceSplit.from_dataset(D.vodDataset(EvalArgs(), a.root, "test"), dev)
-    _, store = EV.test_split(net.to(dev).eval(), sp, 16)
+    from cmflow_amd import _lib, accumulate as A
+    sp, store = P.synthetic_store(a)
+    dev = sp.device
     F = len(sp)
     counts = sp.counts_host[0]
     print("split: %d frames as one clip, %d points (%d moving in the prediction); device: %s; %d rounds, %d calls per stream window"
           % (F, sp.tab1.shape[0], int((store.mask == 0).sum()), torch.cuda.get_device_name(0), a.rounds, a.reps))
-
-    def timed(fn, reps):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(reps):
-            fn()
-        stop.record()
-        stop.synchronize()
-        return 1e3 * start.elapsed_time(stop) / reps                      # us per call
-
     for window in WINDOWS:
         first, ages, cap_off = A.plan(counts, None, np.arange(F), window)
         R = int(cap_off[-1])
@@ -99,15 +76,15 @@ def child(a):
             call = lambda: A.accumulate(sp, store, window=window, dynamic=dynamic)
             acc = call()
             torch.cuda.synchronize()
-            single = statistics.median(timed(call, 1) for _ in range(a.rounds))
-            stream = statistics.median(timed(call, a.reps) for _ in range(a.rounds))
+            single = statistics.median(P.timed(call, 1) for _ in range(a.rounds))
+            stream = statistics.median(P.timed(call, a.reps) for _ in range(a.rounds))
             first_d = torch.from_numpy(first).to(dev)
             p, i32, u8, f32 = _lib.dev_ptr, torch.int32, torch.uint8, torch.float32
             args = (F, F, None, p(first_d, i32), p(sp.off1, i32), sp.tab1.shape[0], p(sp.tab1, f32), sp.tab1.shape[1], p(store.flow, f32),
                     p(store.mask, u8), p(store.pred_trans.reshape(-1, 16), f32), window, A.DYNAMIC.index(dynamic), 0, p(acc.off, i32), R,
                     p(acc.xyz, f32), p(acc.src, i32), p(acc.age, u8), p(acc.count, i32), _lib.stream_ptr())
             entry = _lib.lib().cmf_accumulate
-            kernel = statistics.median(timed(lambda: entry(*args), a.reps) for _ in range(a.rounds))
+            kernel = statistics.median(P.timed(lambda: entry(*args), a.reps) for _ in range(a.rounds))
             held = int(acc.count.sum())
             moved = int(((store.mask[acc.src.clamp(min=0).long()] == 0) & (acc.age >= 1) & (acc.age != 255)).sum()) if dynamic == "propagate" else 0
             nbytes = R * (1 + 17) + held * 12 + moved * 12 + int((ages - 1).sum()) * 48 + F * 8
@@ -115,41 +92,12 @@ def child(a):
             got = ref()
             mine = acc.xyz[acc.src >= 0] if dynamic == "drop" else acc.xyz
             dev_max = float((got - mine).abs().max())
-            t_torch = statistics.median(timed(ref, 5) for _ in range(a.rounds))
+            t_torch = statistics.median(P.timed(ref, 5) for _ in range(a.rounds))
             print("window %2d %-9s %8d rows (%8d hold points): single %7.1f us, stream %7.1f us per call, kernel %7.1f us; %6.2f MB algorithmic -> "
                   "%5.3f TB/s achieved by the kernel, %4.1f%% of 8 TB/s; torch float32 %9.1f us (x%.0f the call), max deviation %.2e m"
                   % (window, dynamic, R, held, single, stream, kernel, nbytes / 1e6, nbytes / kernel / 1e6, 100 * nbytes / (kernel * 1e-6) / PEAK,
                      t_torch, t_torch / stream, dev_max))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--reps", type=int, default=50, help="calls back to back inside one timed window")
-    ap.add_argument("--limit", type=int, default=400, help="seconds for the measurement")
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--root", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a)
-    from cmflow_amd import dataset as D
-    with tempfile.TemporaryDirectory(prefix="cmf_accumulate_probe_") as root:
-        D.write_synthetic_split(root, seed=11, clips=clips_of(a.frames))
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--frames", str(a.frames),
-               "--rounds", str(a.rounds), "--reps", str(a.reps)]
-        try:
-            done = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit("accumulate_probe: the measurement did not finish in %d s" % a.limit)
-        sys.stdout.write(done.stdout)
-        if done.returncode != 0:
-            raise SystemExit("accumulate_probe: the measurement ended with status %d" % done.returncode)
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write(done.stdout)
-
-
 if __name__ == "__main__":
-    main()
+    P.run("accumulate_probe", measure, (("--rounds", 9, None), ("--reps", 50, P.REPS_HELP)))

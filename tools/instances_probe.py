@@ -19,17 +19,12 @@ measurement is a child process under a time limit.
 
     python tools/instances_probe.py [--frames 256] [--rounds 9] [--reps 50] [--limit 400] [--out profiles/instances_probe.txt]
 """
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from tools.results_probe import EvalArgs, clips_of             # noqa: E402  (the same split as the results probe)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import _run_probe as P                               # noqa: E402
 
 SETTINGS = ((2.0, 2, 0.0), (2.0, 2, 2.5))                       # eps, min_points, flow_weight
 
@@ -70,40 +65,21 @@ def torch_labels(sp, flow, moving, T, eps, min_points, weight):
     return inst[valid]
 
 
-def child(a):
+def measure(a):
     import torch
-    from cmflow_amd import _lib, dataset as D, evaluate as EV, instances as I, synth
-    from cmflow_amd.cmflow import CMFlow
-    if not torch.cuda.is_available():
-        raise SystemExit("instances_probe: needs the GPU")
-    dev = torch.device("cuda:0")
-    gold = os.path.join(REPO, "tests", "golden")
-    net = CMFlow(EvalArgs())
-    net.load_state_dict(synth.synth_state_dict(json.load(open(os.path.join(gold, "state_manifest_cmflow.json"))), seed=1234,
-                                               calib=os.path.join(gold, "bn_calib_cmflow.npz")))
-    sp = D.DeviceSplit.from_dataset(D.vodDataset(EvalArgs(), a.root, "test"), dev)
-    _, store = EV.test_split(net.to(dev).eval(), sp, 16)
+    from cmflow_amd import _lib, instances as I
+    sp, store = P.synthetic_store(a)
     F, counts = len(sp), sp.counts_host[0]
     print("split: %d frames of %d-%d points, %d points (%d moving in the prediction, %d in the labels); device: %s; %d rounds, %d calls per "
           "stream window" % (F, counts.min(), counts.max(), sp.tab1.shape[0], int((store.mask == 0).sum()), int((sp.tab1[:, 9] == 0).sum()),
                              torch.cuda.get_device_name(0), a.rounds, a.reps))
-
-    def timed(fn, reps):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(reps):
-            fn()
-        stop.record()
-        stop.synchronize()
-        return 1e3 * start.elapsed_time(stop) / reps                      # us per call
-
     for which in I.WHICH:
         for eps, min_points, weight in SETTINGS:
             call = lambda: I.cluster(sp, store if which == "pred" else None, which=which, eps=eps, min_points=min_points, flow_weight=weight)
             inst = call()
             torch.cuda.synchronize()
-            single = statistics.median(timed(call, 1) for _ in range(a.rounds))
-            stream = statistics.median(timed(call, a.reps) for _ in range(a.rounds))
+            single = statistics.median(P.timed(call, 1) for _ in range(a.rounds))
+            stream = statistics.median(P.timed(call, a.reps) for _ in range(a.rounds))
             p, i32, u8, f32 = _lib.dev_ptr, torch.int32, torch.uint8, torch.float32
             gt = which == "gt"
             flow, mask, T = (None, None, sp.trans) if gt else (store.flow, store.mask, store.pred_trans)
@@ -112,11 +88,11 @@ def child(a):
                     p(inst.count, i32), p(inst.size, i32), p(inst.seed, i32), p(inst.centroid, f32), p(inst.disp, f32), p(inst.lo, f32),
                     p(inst.hi, f32), _lib.stream_ptr())
             entry = _lib.lib().cmf_cluster_moving
-            kernel = statistics.median(timed(lambda: entry(*args), a.reps) for _ in range(a.rounds))
+            kernel = statistics.median(P.timed(lambda: entry(*args), a.reps) for _ in range(a.rounds))
             t_flow, t_moving = (sp.tab1[:, 6:9], sp.tab1[:, 9] == 0) if gt else (store.flow, store.mask == 0)
             ref = lambda: torch_labels(sp, t_flow, t_moving, T, eps, min_points, weight)
             same = int((ref() == inst.label.long()).sum())
-            t_torch = statistics.median(timed(ref, 3) for _ in range(min(a.rounds, 5)))
+            t_torch = statistics.median(P.timed(ref, 3) for _ in range(min(a.rounds, 5)))
             members = inst.kind >= 2
             print("%-4s eps %.1f min_points %d flow_weight %.1f: %5d instances, %6d member points, %6d noise: single %7.1f us, stream %7.1f us per "
                   "call, kernel %7.1f us; torch float64 %9.1f us (x%.0f the call), %d of %d labels equal"
@@ -124,34 +100,5 @@ def child(a):
                      t_torch, t_torch / stream, same, inst.label.numel()))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--reps", type=int, default=50, help="calls back to back inside one timed window")
-    ap.add_argument("--limit", type=int, default=400, help="seconds for the measurement")
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--root", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a)
-    from cmflow_amd import dataset as D
-    with tempfile.TemporaryDirectory(prefix="cmf_instances_probe_") as root:
-        D.write_synthetic_split(root, seed=11, clips=clips_of(a.frames))
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--frames", str(a.frames),
-               "--rounds", str(a.rounds), "--reps", str(a.reps)]
-        try:
-            done = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit("instances_probe: the measurement did not finish in %d s" % a.limit)
-        sys.stdout.write(done.stdout)
-        if done.returncode != 0:
-            raise SystemExit("instances_probe: the measurement ended with status %d" % done.returncode)
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write(done.stdout)
-
-
 if __name__ == "__main__":
-    main()
+    P.run("instances_probe", measure, (("--rounds", 9, None), ("--reps", 50, P.REPS_HELP)))

@@ -17,43 +17,22 @@ The parent process writes the split and never opens the GPU; the measurement is 
 
     python tools/results_probe.py [--frames 256] [--batch 16] [--epochs 5] [--rounds 7] [--limit 400]
 """
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import _run_probe as P                               # noqa: E402
+from tools._run_probe import EvalArgs, PER_CLIP, clips_of     # noqa: E402,F401  (the other probes' split is this one)
+
 VARIANTS = ("plain", "collector", "per_frame")
-PER_CLIP = 8
 
 
-class EvalArgs:
-    num_points, eval, stat_thres = 256, True, 0.5
-
-
-def clips_of(frames):
-    return tuple(("test", "delft_%d" % (c + 1), tuple(87 + (37 * c + 53 * f) % 375 for f in range(PER_CLIP)))
-                 for c in range(frames // PER_CLIP))
-
-
-def child(a):
+def measure(a):
     import torch
-    from cmflow_amd import dataset as D, evaluate as EV, synth
-    from cmflow_amd.cmflow import CMFlow
-    if not torch.cuda.is_available():
-        raise SystemExit("results_probe: needs the GPU")
-    dev = torch.device("cuda:0")
-    gold = os.path.join(REPO, "tests", "golden")
-    net = CMFlow(EvalArgs())
-    net.load_state_dict(synth.synth_state_dict(json.load(open(os.path.join(gold, "state_manifest_cmflow.json"))), seed=1234,
-                                               calib=os.path.join(gold, "bn_calib_cmflow.npz")))
-    net = net.to(dev).eval()
-    sp = D.DeviceSplit.from_dataset(D.vodDataset(EvalArgs(), a.root, "test"), dev)
+    from cmflow_amd import evaluate as EV
+    net, sp = P.synthetic_net_split(a)
     print("split: %d frames, %d + %d points; device: %s; batch %d; %d rounds of %d epochs per variant, order rotated"
           % (len(sp), sp.tab1.shape[0], sp.tab2.shape[0], torch.cuda.get_device_name(0), a.batch, a.rounds, a.epochs))
 
@@ -90,30 +69,5 @@ def child(a):
           % (statistics.median(total["collector"]) - base, statistics.median(total["per_frame"]) - base))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--epochs", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--limit", type=int, default=400, help="seconds for the measurement")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--root", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a)
-    from cmflow_amd import dataset as D
-    with tempfile.TemporaryDirectory(prefix="cmf_results_probe_") as root:
-        D.write_synthetic_split(root, seed=11, clips=clips_of(a.frames))
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--frames", str(a.frames), "--batch", str(a.batch),
-               "--epochs", str(a.epochs), "--rounds", str(a.rounds)]
-        try:
-            rc = subprocess.run(cmd, timeout=a.limit).returncode
-        except subprocess.TimeoutExpired:
-            raise SystemExit("results_probe: the measurement did not finish in %d s" % a.limit)
-        if rc != 0:
-            raise SystemExit("results_probe: the measurement ended with status %d" % rc)
-
-
 if __name__ == "__main__":
-    main()
+    P.run("results_probe", measure, (("--batch", 16, None), ("--epochs", 5, None), ("--rounds", 7, None)), out=False)

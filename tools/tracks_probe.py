@@ -19,55 +19,29 @@ The parent process writes the split and never opens the GPU; the measurement is 
 
     python tools/tracks_probe.py [--frames 256] [--rounds 9] [--reps 50] [--limit 400] [--out profiles/tracks_probe.txt]
 """
-import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
-from tools.results_probe import EvalArgs, PER_CLIP, clips_of   # noqa: E402  (the same split as the results probe)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import _run_probe as P                               # noqa: E402
 
 GATE, MAX_GAP = 2.0, 2
-WORLD_REPEATS = 16
 
 
-def child(a):
+def measure(a):
     import numpy as np
     import torch
-    import instances_ref as iref
     import tracks_ref as ref
-    from cmflow_amd import _lib, dataset as D, evaluate as EV, instances as I, results as R, synth, tracks as K
-    from cmflow_amd.cmflow import CMFlow
-    if not torch.cuda.is_available():
-        raise SystemExit("tracks_probe: needs the GPU")
-    dev = torch.device("cuda:0")
+    from cmflow_amd import _lib, tracks as K
     print("device: %s; gate %.1f, max_gap %d; %d rounds, %d calls per stream window; median [smallest .. largest round]"
           % (torch.cuda.get_device_name(0), GATE, MAX_GAP, a.rounds, a.reps))
 
-    def timed(fn, reps):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(reps):
-            fn()
-        stop.record()
-        stop.synchronize()
-        return 1e3 * start.elapsed_time(stop) / reps                      # us per call
-
-    def spread(fn, reps):
-        v = [timed(fn, reps) for _ in range(a.rounds)]
-        return "%7.1f [%7.1f .. %7.1f] us" % (statistics.median(v), min(v), max(v))
-
-    def measure(name, sp, store, inst):
+    def case(name, sp, store, inst):                            # its tensors and tables are dropped before the next case
         call = lambda: K.track(inst, sp, store, gate=GATE, max_gap=MAX_GAP)
         tr = call()
         torch.cuda.synchronize()
-        single, stream = spread(call, 1), spread(call, a.reps)
+        single, stream = P.spread(call, 1, a.rounds), P.spread(call, a.reps, a.rounds)
         p, i32, f32 = _lib.dev_ptr, torch.int32, torch.float32
         T = store.pred_trans if inst.which == "pred" else sp.trans
         outs = (tr.track, tr.prev_row, tr.gap, tr.age, tr.pred, tr.point_track, tr.birth, tr.last, tr.hits)
@@ -75,7 +49,7 @@ def child(a):
                 p(inst.disp, f32), p(T.reshape(-1, 16), f32), GATE * GATE, MAX_GAP, *(p(t, f32 if t.dtype == f32 else i32) for t in outs),
                 p(tr.ntracks, i32), p(tr.overflow, i32), _lib.stream_ptr())
         entry = _lib.lib().cmf_track_instances
-        kernel = spread(lambda: entry(*args), a.reps)
+        kernel = P.spread(lambda: entry(*args), a.reps, a.rounds)
         t0 = time.perf_counter()
         off1 = sp.off1.cpu().numpy()
         want = ref.track(off1, int(off1[-1]), inst.count.cpu().numpy(), inst.label.cpu().numpy(), inst.centroid.cpu().numpy(), inst.disp.cpu().numpy(),
@@ -87,64 +61,9 @@ def child(a):
               "%8.1f ms once, outputs %s" % (name, len(tr), int((tr.clips_host[:, 1] - tr.clips_host[:, 0]).max()), inst_n, int(tr.ntracks.sum()), matched,
                                              single, stream, kernel, host, "equal" if same else "DIFFER"))
 
-    # ---- (a) the synthetic partition
-    gold = os.path.join(REPO, "tests", "golden")
-    net = CMFlow(EvalArgs())
-    net.load_state_dict(synth.synth_state_dict(json.load(open(os.path.join(gold, "state_manifest_cmflow.json"))), seed=1234,
-                                               calib=os.path.join(gold, "bn_calib_cmflow.npz")))
-    sp = D.DeviceSplit.from_dataset(D.vodDataset(EvalArgs(), a.root, "test"), dev)
-    _, store = EV.test_split(net.to(dev).eval(), sp, 16)
-    F, counts = len(sp), sp.counts_host[0]
-    print("synthetic partition (frames not coherent in time): %d frames of %d-%d points" % (F, counts.min(), counts.max()))
-    for which in I.WHICH:
-        inst = I.cluster(sp, store if which == "pred" else None, which=which)
-        for clips in ([(c, min(c + PER_CLIP, F)) for c in range(0, F, PER_CLIP)], None):
-            sp.clips = clips
-            measure("synthetic %-4s %s" % (which, "clips of %d" % PER_CLIP if clips else "one clip"), sp, store, inst)
-    # ---- (b) the coherent world, repeated
-    frames, _ = ref.build_world()
-    n = len(frames)
-    frames = frames * WORLD_REPEATS
-    clips = [(r * n + c0, r * n + c1) for r in range(WORLD_REPEATS) for c0, c1 in ref.WORLD_CLIPS]
-    wsp = D.DeviceSplit.from_items(iref.as_items(frames), dev, clips)
-    wst = R.SplitResults.empty(wsp)
-    wst.flow.copy_(torch.from_numpy(np.concatenate([fr["flow"] for fr in frames])))
-    wst.mask.copy_(torch.from_numpy(np.concatenate([fr["mask"] for fr in frames])))
-    wst.pred_trans.copy_(torch.from_numpy(np.stack([fr["pred_t"] for fr in frames])))
-    wst.done.fill_(1)
-    print("coherent world: %d frames of %d-%d points" % (len(wsp), wsp.counts_host[0].min(), wsp.counts_host[0].max()))
-    for which in I.WHICH:
-        measure("coherent  %-4s" % which, wsp, wst, I.cluster(wsp, wst if which == "pred" else None, which=which))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--reps", type=int, default=50, help="calls back to back inside one timed window")
-    ap.add_argument("--limit", type=int, default=400, help="seconds for the measurement")
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--root", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a)
-    from cmflow_amd import dataset as D
-    with tempfile.TemporaryDirectory(prefix="cmf_tracks_probe_") as root:
-        D.write_synthetic_split(root, seed=11, clips=clips_of(a.frames))
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--frames", str(a.frames),
-               "--rounds", str(a.rounds), "--reps", str(a.reps)]
-        try:
-            done = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit("tracks_probe: the measurement did not finish in %d s" % a.limit)
-        sys.stdout.write(done.stdout)
-        if done.returncode != 0:
-            raise SystemExit("tracks_probe: the measurement ended with status %d" % done.returncode)
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write(done.stdout)
+    for name, sp, store, inst in P.tracking_cases(a):
+        case(name, sp, store, inst)
 
 
 if __name__ == "__main__":
-    main()
+    P.run("tracks_probe", measure, (("--rounds", 9, None), ("--reps", 50, P.REPS_HELP)))

@@ -15,35 +15,22 @@ time limit.
 
     python tools/vis_probe.py [--frames 256] [--chunk 64] [--rounds 5] [--reps 100] [--limit 400] [--out profiles/vis_probe.txt]
 """
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from tools.results_probe import EvalArgs, clips_of             # noqa: E402  (the same split as the results probe)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import _run_probe as P                               # noqa: E402
 
 LAYERS = ("flow", "seg_gt")
 
 
-def child(a):
+def measure(a):
     import torch
-    from cmflow_amd import dataset as D, evaluate as EV, synth, vis
-    from cmflow_amd.cmflow import CMFlow
-    if not torch.cuda.is_available():
-        raise SystemExit("vis_probe: needs the GPU")
-    dev = torch.device("cuda:0")
-    gold = os.path.join(REPO, "tests", "golden")
-    net = CMFlow(EvalArgs())
-    net.load_state_dict(synth.synth_state_dict(json.load(open(os.path.join(gold, "state_manifest_cmflow.json"))), seed=1234,
-                                               calib=os.path.join(gold, "bn_calib_cmflow.npz")))
-    net = net.to(dev).eval()
-    sp = D.DeviceSplit.from_dataset(D.vodDataset(EvalArgs(), a.root, "test"), dev)
+    from cmflow_amd import evaluate as EV, vis
+    net, sp = P.synthetic_net_split(a)
     EV.test_split(net, sp, 16)                                  # warm-up of the forward
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -102,35 +89,6 @@ def child(a):
           % (1e3 * dev_s / n, 1e3 * enc_s / n, 1e3 * file_s / n))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--chunk", type=int, default=64)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=100, help="passes over the split inside one timed window of render")
-    ap.add_argument("--limit", type=int, default=400, help="seconds for the measurement")
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--root", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a)
-    from cmflow_amd import dataset as D
-    with tempfile.TemporaryDirectory(prefix="cmf_vis_probe_") as root:
-        D.write_synthetic_split(root, seed=11, clips=clips_of(a.frames))
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--frames", str(a.frames), "--chunk", str(a.chunk),
-               "--rounds", str(a.rounds), "--reps", str(a.reps)]
-        try:
-            done = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit("vis_probe: the measurement did not finish in %d s" % a.limit)
-        sys.stdout.write(done.stdout)
-        if done.returncode != 0:
-            raise SystemExit("vis_probe: the measurement ended with status %d" % done.returncode)
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write(done.stdout)
-
-
 if __name__ == "__main__":
-    main()
+    P.run("vis_probe", measure, (("--chunk", 64, None), ("--rounds", 5, None),
+                                 ("--reps", 100, "passes over the split inside one timed window of render")))
