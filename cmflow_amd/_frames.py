@@ -1,6 +1,7 @@
-"""What the stages of a test run's analysis chain (``accumulate``, ``instances``, ``tracks``, ``objects``, ``vis``) ask of their
-arguments, stated once: the ``which`` of a stage, the store or the upstream result that must belong to the split, numbers in their
-ranges, the frame selection, the ``done`` test, the (flow, mask, transforms) a stage reads, and the pinned upload of host tables.
+"""What the stages of a test run's analysis chain (``accumulate``, ``instances``, ``tracks``, ``objects``, ``score``, ``vis``) ask of
+their arguments, stated once: the ``which`` of a stage, the store or the upstream result that must belong to the split, the two sides
+``score`` compares, numbers in their ranges, the frame selection, the ``done`` test, the (flow, mask, transforms) a stage reads, and
+the pinned upload of host tables.
 Every check takes the caller's name (``what``) for its message.  A stage calls them in its own order -- every ``ValueError`` first,
 then ``bind`` / ``on_device`` for the ``RuntimeError``s -- so nothing here touches the device before those two.  Private: the stages'
 docstrings are the contract.  The device side of the same rules is csrc/frame_tables.h.
@@ -32,6 +33,13 @@ def number(what, name, v, zero_ok, says):
     """``v`` as a float: a finite int or float (numpy's included, no bool) above 0, or 0 and above with ``zero_ok``; ``says``: the
     range in words, for the message."""
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+        raise ValueError("%s: %s = %r (%s)" % (what, name, v, says))
+    return float(v)
+
+
+def within(what, name, v, lo, hi, says):
+    """``v`` as a float: a finite int or float (numpy's included, no bool) in [lo, hi); ``says``: the range in words."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or not lo <= v < hi:
         raise ValueError("%s: %s = %r (%s)" % (what, name, v, says))
     return float(v)
 
@@ -90,6 +98,20 @@ def check_upstream(split, store, result, rows, what, these, made):
         raise ValueError("%s: the split is not the one these %s belong to" % (what, these))
     if result.which == "pred":
         belongs(split, store, what)
+
+
+def check_sides(split, a, b, what, these):
+    """Two results of one stage (``these``: 'object states') that a stage compares: both in the split's row space (as
+    ``check_upstream``), with the same offsets and the same clips, on one device."""
+    for r in (a, b):
+        if len(split) != r.off.numel() - 1 or split.tab1.shape[0] != r.trk.track.shape[0]:
+            raise ValueError("%s: the split is not the one these %s belong to" % (what, these))
+    if not np.array_equal(a.offsets_host, b.offsets_host):
+        raise ValueError("%s: the two sides' offsets differ: not the same split" % what)
+    if not np.array_equal(a.clips_host, b.clips_host):
+        raise ValueError("%s: the two sides were tracked over different clips" % what)
+    if a.device != b.device:
+        raise ValueError("%s: the two sides lie on different devices (%s, %s)" % (what, a.device, b.device))
 
 
 def need_done(store, needed, what, role):

@@ -174,6 +174,9 @@ SIGNATURES = {
     "cmf_track_states": [_ci, _ci, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp,
                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # two sides of the chain scored against each other: matches, id switches, fragmentations (score.py)
+    "cmf_score_tracks": [_ci, _ci, _vp, _vp, _ll, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cmf_debug_spin": [_cf, _vp],
     "cmf_eval_metrics": [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp],
 }

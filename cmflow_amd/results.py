@@ -280,6 +280,23 @@ class SplitResults:
             raise ValueError("SplitResults.objects: %s belong to the tracks, which were given" % ", ".join(sorted(kw)))
         return O.estimate(trk, split, self, **own)
 
+    def score_tracks(self, split, iou=0.5, pred=None, gt=None, **kw):
+        """``score.score(pred, gt, split, iou)``: the predicted chain's tracks and objects scored against the labels'.  ``pred`` /
+        ``gt``: ``objects`` results of this split, or None -- then ``self.objects(split, which='pred' / 'gt', ...)`` is formed first
+        from the remaining keywords, both sides with the same options (``'gt'`` reads no store).  (Not ``score``: that is the store's
+        per-point classification score.)"""
+        from . import score as S
+        S.check_iou(iou)                                                    # before the chains launch anything
+        if "which" in kw:
+            raise ValueError("SplitResults.score_tracks: which = %r -- the two sides are 'pred' and 'gt'; pass pred= / gt= for others" % (kw["which"],))
+        if pred is not None and gt is not None and kw:
+            raise ValueError("SplitResults.score_tracks: %s belong to the object states, which were given" % ", ".join(sorted(kw)))
+        if pred is None:
+            pred = self.objects(split, which="pred", **kw)
+        if gt is None:
+            gt = self.objects(split, which="gt", **kw)
+        return S.score(pred, gt, split, iou=iou)
+
     # ---- odometry ---------------------------------------------------------------------------------------------------------------------
     def trajectories(self, which="pred"):
         """(F,4,4) float64: the sensor's pose at every frame relative to its clip's first scan, ``cmf_pose_chain`` over ``pred_trans``

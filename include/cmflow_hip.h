@@ -1304,6 +1304,63 @@ int cmf_track_states(int nclips, int nframes, const int *clips, const int *off1,
                      int *row_frame, int *next_row, double *filt, double *fcov, double *state, double *scov, float *pos, float *vel,
                      float *heading, int *heading_src, float *box_center, float *box_size, void *stream);
 
+/* ---- two sides of the analysis chain scored against each other (cmflow_amd/score.py) ------------------------------
+ * cmf_score_tracks: per frame the instances of a "gt" and a "pred" side of the chain (cmf_cluster_moving .. cmf_track_instances on the
+ * SAME split) matched by their point overlap, and per clip the identity walk of MOTS over the gt side's tracks -- a definition, not
+ * an approximation of one.  Integers everywhere but one float64 division per candidate pair.
+ *   clips, off1, total: as cmf_track_instances takes them.  iou_min in [0.5, 1).  gt_count / pred_count (nframes), gt_label /
+ *   pred_label (total) int32: cmf_cluster_moving's count and label of either side (a frame a side did not select has count 0 there);
+ *   gt_track / pred_track, gt_prev_row (total) int32: cmf_track_instances' track of either side and the gt side's prev_row.  The
+ *   size tables are not read.
+ * Rows: the clamping of a clip, base, top and the frames that OWN rows are those of cmf_track_instances, word for word; in a frame
+ *   that owns its n_f rows, K_side = count_side[f] clamped to [0, min(n_f, 1024)], except that a frame of more than
+ *   CMF_INST_MAX_POINTS rows has K = 0 on both sides (cmf_cluster_moving gives it no instances).  A frame that owns no rows has no
+ *   instances on either side.  SOLID, the clip's gap-free rows: solid = base at the start, and a frame that owns [start, stop) with
+ *   start == solid moves solid to stop.  For offsets that ascend inside the tables solid == top throughout: every row of the clip
+ *   so far.  (Only a frame that owns no rows in the middle of a clip leaves rows behind solid.)
+ * Per frame, over its points i = 0 .. n_f - 1:
+ *   Labels.   g_i = gt_label[row0 + i] where 0 <= gt_label < K_gt, else -1; p_i likewise from the pred side.
+ *   Sizes.    |G| = the points with g_i == G, |P| = those with p_i == P, c(G,P) = those with both: counted from the labels.
+ *   Matching. G and P MATCH iff c > 0 and (double)c / (double)(|G| + |P| - c) > iou_min: one float64 division, a strict compare.
+ *             At most one P passes for a G and one G for a P: a correctly rounded quotient is monotone and 1/2 is a float64, so a
+ *             pair that passes has c / (|G| + |P| - c) > 1/2 as rationals, i.e. 3c > |G| + |P|; with c <= |P| this gives 2c > |G| --
+ *             P holds more than half of G's points, and the instances of a side are disjoint, so no second P does; the same with G
+ *             and P exchanged.  No assignment problem, no greedy order: the result does not depend on any order.
+ *   Outputs in the instances' row space: match[row0 + P] = row0 + G or -1 and iou[row0 + P] = that quotient or 0.0, on pred rows;
+ *             match_gt[row0 + G] = row0 + P or -1 on gt rows.  frame_tp[f] = the matched pairs, frame_fp[f] = K_pred - tp,
+ *             frame_fn[f] = K_gt - tp; a frame of the clip that owns no rows gets 0, 0, 0.
+ *   Identity, over the gt instances G = 0 .. K_gt - 1 in ascending order, t = gt_track[row0 + G]: G HAS IDENTITY iff t >= 0 and base + t
+ *             < solid (solid with this frame taken in) and no lower instance of the frame carries the same t.  An instance without
+ *             identity counts in tp / fp / fn and gt_total and in nothing below.  The track's row is base + t (the clip's row space,
+ *             as cmf_track_instances' birth / last / hits): seen += 1; and if G matched P, with u = pred_track[row0 + P] where that is
+ *             >= 0 and base + u < solid, else -1:
+ *               if covered > 0 (the track was matched before):
+ *                  switch[row0 + G] = last_partner != u                        -- the id switch of MOTS
+ *                  frag[row0 + G]   = NOT (base <= r < row0 and r < solid and match_gt[r] >= 0), r = gt_prev_row[row0 + G]
+ *                                                                            -- the track's instance directly before was not matched
+ *               covered += 1, last_partner = u.
+ *             switch and frag are 0 wherever this does not set them.
+ *   The rows of an owned frame behind K_pred hold match -1 and iou 0, those behind K_gt match_gt -1, switch 0, frag 0; seen, covered
+ *   and last_partner of a frame's rows start at 0, 0, -1 when the frame is reached.
+ * Per clip (nclips): tp, fp, fn, gt_total (the sum of K_gt) int32, the sums over its frames; ids, frags int32, the sums of switch
+ *   and frag; iou_units int64, the sum over the matches of (long long)floor(iou * 2^30) -- integers, exact in any order.
+ * Guarantees, as cmf_track_states: no global scratch; every element of an owned frame's rows, every frame_* entry of a clip's frames
+ *   and every per-clip entry is written, rows and frames outside every clip are not touched; for ANY tables the result is wrong
+ *   data at worst, never an access outside a buffer and never an unbounded loop: a label indexes a table only after it is clamped to
+ *   the frame's K, a track only after base + t < solid, which is a row of an owned frame of this clip at or before the current one,
+ *   prev_row only after it is found inside the clip's solid rows before the frame, and every loop runs over a frame's rows or
+ *   the workgroup's threads.  Clips that overlap write the same rows more than once.  total <= INT_MAX.
+ *   One workgroup of 1024 threads per clip, its frames in sequence: one thread per point and per instance, the labels as packed keys
+ *   in LDS, |G| and |P| by LDS integer atomics, c by a scan of the frame's keys (every lane reads the same address: a broadcast), the
+ *   passing pairs published by LDS atomicMax (all points of a pair publish the same numbers); a gt track is touched by one thread
+ *   per frame, and a frame reads the per-track rows the frames before wrote behind a barrier.  28 KB of LDS, no scratch.  The launch
+ *   keeps nclips CUs busy and lasts as long as its longest clip.  tests/score_ref.py restates all of this in numpy, bit for bit. */
+int cmf_score_tracks(int nclips, int nframes, const int *clips, const int *off1, long long total, double iou_min,
+                     const int *gt_count, const int *gt_label, const int *gt_track, const int *gt_prev_row, const int *pred_count,
+                     const int *pred_label, const int *pred_track, int *match, int *match_gt, double *iou, int *switches, int *frag,
+                     int *frame_tp, int *frame_fp, int *frame_fn, int *seen, int *covered, int *last_partner, int *tp, int *fp,
+                     int *fn, int *ids, int *frags, int *gt_total, long long *iou_units, void *stream);
+
 /* Library / device identification: returns a static NUL-terminated string. */
 const char *cmf_version(void);
 

@@ -1,12 +1,12 @@
 """What the probes of a test run's analysis chain share (results_probe, vis_probe, accumulate_probe, instances_probe, tracks_probe,
-objects_probe): the parent/child runner, the timing of a call between two device events, and the two fixtures they measure on.
+objects_probe, score_probe): the parent/child runner, the timing of a call between two device events, and the two fixtures they measure on.
 
     run(name, measure, options)   the parent parses the command line, writes the synthetic split and never opens the GPU; the
                                   measurement -- measure(a), a.root the split's directory -- is a child process under --limit
     timed / spread                us per call between two device events; spread: median [smallest .. largest round]
     synthetic_net_split / synthetic_store   the synthetic test partition, the synthetic-weights net, its evaluation epoch's store
     coherent_world / tracking_cases         the coherent world of tests/tracks_ref.py repeated, with its filled store; the cases
-                                  tracks_probe and objects_probe go through on both
+                                  tracks_probe, objects_probe and score_probe go through on both
 """
 import argparse
 import json
